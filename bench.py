@@ -13,7 +13,13 @@ decisions/s = groups x steps / time. Every timed step runs on its own pristine
 copy of the state (a tick mutates the state; re-running it on mutated state
 would be a different, lighter workload).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]. For N > 1 either launch
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+[--full]. A plain run sets up, warms up, times the K steps and prints the
+result line; --dump-outputs DIR then also writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs); --full adds, after the timed region,
+everything else the benchmark measures or checks (the sharded tick against one
+launch, the placement probe, the secondary configurations, the CPU baseline).
+For N > 1 either launch
 with torch.distributed.run (one process per GPU) or let bench.py start the N
 rank processes itself; N > 1 defaults to BASELINE config #4 (262,144 groups
 split over the GPUs, strong scaling) with one RCCL all-gather of the GetState
@@ -1008,6 +1014,33 @@ def stream_plan(shards: int, rccl: bool, fanin_cus: int, fanin: str) -> dict:
     return plan
 
 
+DUMP_MAX_ELEMS = 384 * 1024  # per array, as float64: 3 MiB; 18 arrays stay under 64 MB
+DUMP_SEED = 0xD0D0
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the last timed step computed, one `<name>.npy`
+    (float64, exact for int32) per array in `arrays` (name -> 1-D int32 device
+    tensor): the tick's return arrays (group flags, the exported GetState
+    words) and the state copy it ticked in place. An array of more than
+    DUMP_MAX_ELEMS elements is written as a fixed sample of that many: the
+    elements at sorted indices drawn from a generator seeded by DUMP_SEED and
+    the array's name, the same in every run and build."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, *name.encode()]).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy().astype(np.float64)
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 * 10**6, total
+    return total
+
+
 def spawn_ranks(n: int) -> int:
     """`--gpus N` without a launcher: start N rank processes (one per GPU) and
     wait for them. The parent never touches the GPU (it only forwards the
@@ -1057,10 +1090,19 @@ def main():
                          "(cache-resident: not an HBM measurement)")
     ap.add_argument("--peers", type=int, default=5)
     ap.add_argument("--log", type=int, default=4096, help="log capacity L")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (group flags, "
+                         "exported GetState words, the ticked state copy) as DIR/<name>.npy, float64, at "
+                         "most 64 MB (large arrays as a fixed seeded sample); rank 0 only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beside the headline: the sharded "
+                         "tick checked against one launch, the placement probe, the secondary lines "
+                         "and the CPU baseline (a plain run does none of these)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary lines (message path, configs #5 and #2) of a one-GPU run")
+                    help="with --full: skip the secondary lines (message path, configs #5 and #2) of a "
+                         "one-GPU run")
     ap.add_argument("--pmc-json", default="",
                     help="PMC traffic summary (default: profiles/pmc_traffic.json for 65,536 groups "
                          "per GPU, profiles/pmc_traffic_g<G>.json otherwise)")
@@ -1192,7 +1234,8 @@ def main():
             master = {k: torch.from_numpy(v).to(dev) for k, v in st.items()}
             clone_bytes = sum(v.numel() * 4 for v in master.values())
             free, _ = torch.cuda.mem_get_info(dev)
-            pool = max(1, min(K + 1, int(free * 0.9 // clone_bytes)))
+            # (--full: the secondary lines run on up to 9 of these copies, however few the steps)
+            pool = max(1, min(max(K + 1, 9) if args.full else K + 1, int(free * 0.9 // clone_bytes)))
             clones = [{k: v.clone() for k, v in master.items()} for _ in range(pool)]
             torch.cuda.synchronize()
         if dist_on:
@@ -1341,7 +1384,16 @@ def main():
     # the last shard's end
     span_ms = max(t_begin.elapsed_time(e) for e in t_end)
     launch_ms = [[mark_start(i, si).elapsed_time(mark_end(i, si)) for i in range(K)] for si in range(S)]
-    if S > 1:
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs: what replicate_tick_export returned
+        # and the state copy it ticked (before anything below reuses the copies)
+        last = clones[(K - 1) % pool] if restore else clones[K - 1]
+        nbytes = dump_outputs(args.dump_outputs,
+                              {"group_flags": gf_d, "status_commit": status[K - 1, :G],
+                               "status_term_leader": status[K - 1, G:],
+                               **{"state_" + k: v for k, v in last.items()}})
+        log(rank, f"wrote the last step's outputs to {args.dump_outputs} ({nbytes / 1e6:.1f} MB)")
+    if S > 1 and args.full:
         # the shards' last step (a pristine copy) equals one launch over every
         # group on the same input: flags and export words
         ck = clones[K]
@@ -1467,7 +1519,7 @@ def main():
     if world > 1:
         out["roofline"]["kernel_ms_mean_max_over_ranks"] = ker_max_ms
     out.update(strong_scaling_ref(strong, world, G_total, S))
-    if world == 1 and not restore:
+    if args.full and world == 1 and not restore:
         pp = placement_probe(clones[:K], G, P, L, dev)
         if pp is not None:
             # the two populations the probe separates (two-means on its times),
@@ -1493,8 +1545,8 @@ def main():
                 pp["populations"] = pops
                 pp["corr_with_kernel_ms" if S == 1 else "corr_with_apportioned_ms"] = float(np.corrcoef(pm, km)[0, 1])
             out["roofline"]["placement_probe"] = pp
-    if (world == 1 and args.config == 3 and not args.no_secondary and G == 65536 and P == 5 and L == 4096
-            and fan is None):
+    if (args.full and world == 1 and args.config == 3 and not args.no_secondary and G == 65536 and P == 5
+            and L == 4096 and fan is None):
         out["secondary"] = secondary(master, clones, lp, G, P, L, stream, dev,
                                      dt / K * 1e3)  # reuses the spent copies
         # config #4's N = 1 anchor: free config #3's copies, then all 262,144 groups on this GPU
@@ -1509,7 +1561,7 @@ def main():
             log(rank, f"config #4 on one GPU, {sk} shard(s): {c['ms_per_step']:.4f} ms/step, device "
                       f"{c['roofline']['kernel_ms_mean']:.4f} ms ({c['roofline']['frac']:.3f} of 8 TB/s) over "
                       f"{c4['steps']} fresh copies")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # at N = 1 only (the driver's N > 1 lines carry cpu_baseline null)
         out["cpu_baseline"] = cpu_baseline(G_total, P, L, seed, args.cpu_seconds, rank)
     if rank == 0:

@@ -17,7 +17,7 @@ for st in ${DO:-tests bench}; do
       rc=$?; tail -3 "$OUT/pytest.log"; [ $rc -eq 0 ] || { grep -E "FAIL|Error" "$OUT/pytest.log" | head -20; exit 1; } ;;
     bench)
       echo "== bench ${BENCH:-}"
-      timeout -k 10 600 python3 -u bench.py ${BENCH:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout -k 10 600 python3 -u bench.py --full ${BENCH:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
       rc=$?; tail -4 "$OUT/bench.err"; [ $rc -eq 0 ] || exit 1
       python3 tools/summarize_bench.py "$OUT/bench.json" ;;
     bench2|bench3)

@@ -1,6 +1,6 @@
 """Writes profiles/config4_n1_anchor.json (read by bench.py's N > 1 lines as
 strong_scaling_reference_ms, matched by tick shards per GPU) from a one-GPU
-bench.py result line that carries secondary.config4_one_gpu.
+`bench.py --full` result line (it carries secondary.config4_one_gpu).
 
 Usage: python tools/write_anchor.py <bench_output.json> <tag>
 """
