@@ -510,11 +510,14 @@ int64_t mraft_tick_light_fallbacks(mraft_engine *h);
  * counts[g] < 0: MRAFT_ITEM_BAD_SLOT), then mraft_replicate_tick runs on the
  * result. out_index / out_term / out_is_leader / item_err are per group (G
  * each), mraft_start's per-item outputs; a group whose leader_peer is out of
- * range starts nothing (-1, -1, 0; MRAFT_ITEM_BAD_SLOT when leader_peer >= P
- * and counts[g] != 0). Equivalent to mraft_start over those slots followed by
- * mraft_replicate_tick; when the light tick runs (MRAFT_TICK_LIGHT, or AUTO
- * choosing it) Start is done inside its first launch, otherwise as its own
- * launch before the full tick. group_flags optional. */
+ * range starts nothing (-1, -1, 0): leader_peer[g] >= P with counts[g] != 0,
+ * negative included, is MRAFT_ITEM_BAD_SLOT; leader_peer[g] < 0 is an idle
+ * group and reports no error whatever counts[g] holds (the negative-count
+ * rule above is for leader_peer[g] in [0, P) only). Equivalent to mraft_start
+ * over those slots followed by mraft_replicate_tick; when the light tick runs
+ * (MRAFT_TICK_LIGHT, or AUTO choosing it) Start is done inside its first
+ * launch, otherwise as its own launch before the full tick. group_flags
+ * optional. */
 int mraft_start_and_tick(mraft_engine *h, const int32_t *leader_peer,
                          const int32_t *counts, int32_t *out_index,
                          int32_t *out_term, int32_t *out_is_leader,
