@@ -656,6 +656,144 @@ int mraft_process_vote_replies(mraft_engine *h, const mraft_rv_result *items,
 int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask,
                           int32_t rounds, int32_t *group_flags, int32_t where);
 
+/* ---- timers (ticker, raft.go:106-125; the timers of :38-50, 66-67) ------- */
+
+/* Optional capabilities of this build, a bitmask (the ABI version says which
+ * structs and entry points exist; a feature bit says a later addition that
+ * changed none of them is present). */
+enum { MRAFT_FEATURE_TIMERS = 1 };
+int32_t mraft_features(void);
+
+/* Timer state: per replica slot the absolute time, in caller-defined clock
+ * ticks, at which its election timer and its heartbeat timer expire
+ * (electionTimer / heartbeatTimer, raft.go:38-39). int32[G*P] each. Not part
+ * of mraft_soa: the engine holds them in buffers of its own once
+ * mraft_timers_enable has run. A timer is due when due <= now. */
+typedef struct {
+  int32_t *election_due;
+  int32_t *heartbeat_due;
+} mraft_timers_soa;
+
+/* StableHeartbeatTimeout / RandomizedElectionTimeout (raft.go:42-50) in clock
+ * ticks: the heartbeat period and the election timeout's range
+ * [election_lo, election_hi). heartbeat in [1, 2^30), 1 <= election_lo <
+ * election_hi <= 2^20; every `now` a timer call takes is in [0, 2^30]
+ * (deadlines stay int32). Anything else is MRAFT_E_INVAL. */
+typedef struct {
+  uint32_t seed;
+  int32_t heartbeat;
+  int32_t election_lo;
+  int32_t election_hi;
+} mraft_timer_config;
+
+/* The election timeout a reset of replica `slot` at time `now` draws. The
+ * reference seeds a fresh generator from the clock on every call
+ * (raft.go:46-50); here the draw is a stateless hash, all uint32 arithmetic:
+ *   fmix(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16
+ *   draw = election_lo + fmix(fmix(slot * 0x9E3779B9 + now) ^ seed) % (election_hi - election_lo)
+ * so two resets of one replica at the same `now` give the same deadline (a
+ * duplicate item in a batch is harmless). "Election reset at now":
+ * election_due = now + draw(slot, now); "heartbeat reset": heartbeat_due =
+ * now + heartbeat. Host code (no GPU needed); -1 on a bad configuration. */
+int32_t mraft_timer_draw(const mraft_timer_config *cfg, int64_t slot, int32_t now);
+
+/* Allocates the timer arrays and arms both timers of every slot at `now`
+ * (Make's two NewTimer calls, raft.go:66-67). Calling it again re-arms every
+ * slot with the new configuration. Before it (and after
+ * mraft_timers_disable), every other timer call returns MRAFT_E_NOSTATE.
+ * Nothing is attached to the handle unless every allocation and the arming
+ * launch succeeded. mraft_destroy frees the arrays. */
+int mraft_timers_enable(mraft_engine *h, const mraft_timer_config *cfg, int32_t now);
+int mraft_timers_disable(mraft_engine *h);
+/* Copy both arrays into / out of the engine (NULL members are skipped). */
+int mraft_timers_load(mraft_engine *h, const mraft_timers_soa *src, int32_t where);
+int mraft_timers_store(mraft_engine *h, const mraft_timers_soa *dst, int32_t where);
+/* Arms both timers of n slots at `now`, as Make does for a restarted replica
+ * (call it after mraft_restore). Slots outside [0, G*P) are skipped. */
+int mraft_timers_arm(mraft_engine *h, const int32_t *slots, int64_t n, int32_t now,
+                     int32_t where);
+
+/* ticker() (raft.go:106-125) for every slot at time `now`:
+ *  - a due election timer is reset (:111); when the replica is not Leader its
+ *    slot is listed in out_election_slots (:112-114: what mraft_start_election
+ *    takes);
+ *  - a due heartbeat timer is reset (:118); when the replica is Leader its
+ *    slot is listed in out_heartbeat_slots (:119-121: the leaders whose
+ *    followers mraft_gather_append_args fans out to).
+ * Both lists are in ascending slot order, with the buffer convention of
+ * mraft_collect_apply_compact: *out_n_e / *out_n_h get the full counts, the
+ * first min(n, cap) slots are written, and a slot that is listed but not
+ * written keeps its due timer for the next call. A list pointer may be NULL
+ * when its cap is 0. */
+int mraft_ticker(mraft_engine *h, int32_t now, int32_t *out_election_slots, int64_t cap_e,
+                 int64_t *out_n_e, int32_t *out_heartbeat_slots, int64_t cap_h,
+                 int64_t *out_n_h, int32_t where);
+
+/* The reference's timer resets that follow a message-path call, taken from
+ * the arrays that call returned: for item i with item_err[i] == 0 (item_err
+ * NULL: every item) and records[i].slot in [0, G*P), at time `now`
+ *   kind                    records          outcome         reset
+ *   MRAFT_NOTE_AE_HANDLED   mraft_ae_args    mraft_ae_reply  election, when reply.term <= args.term
+ *                           (raft_append_entry.go:121: every call that is not stale, the
+ *                           prev < dummy reply with Term 0 of :124 included)
+ *   MRAFT_NOTE_IS_HANDLED   mraft_is_args    mraft_is_reply  election, when reply.term <= args.term
+ *                           (raft_snapshot.go:30)
+ *   MRAFT_NOTE_RV_HANDLED   mraft_rv_args    mraft_rv_reply  election, when vote_granted
+ *                           (raft_election.go:72)
+ *   MRAFT_NOTE_AE_FOLDED    mraft_ae_result  int32 out_flags election, on MRAFT_F_STEPPED_DOWN
+ *                           (raft_append_entry.go:71)
+ *   MRAFT_NOTE_IS_FOLDED    mraft_is_result  int32 out_flags election, on MRAFT_F_STEPPED_DOWN
+ *                           (raft_snapshot.go:63)
+ *   MRAFT_NOTE_RV_FOLDED    mraft_rv_result  int32 out_flags heartbeat, on MRAFT_F_BECAME_LEADER
+ *                           (raft_election.go:39; the tally's step-down, :43-45, resets nothing)
+ * Items may repeat a slot. */
+enum {
+  MRAFT_NOTE_AE_HANDLED = 0,
+  MRAFT_NOTE_IS_HANDLED = 1,
+  MRAFT_NOTE_RV_HANDLED = 2,
+  MRAFT_NOTE_AE_FOLDED = 3,
+  MRAFT_NOTE_IS_FOLDED = 4,
+  MRAFT_NOTE_RV_FOLDED = 5
+};
+int mraft_timers_note(mraft_engine *h, int32_t kind, const void *records, const void *outcome,
+                      const int32_t *item_err, int64_t n, int32_t now, int32_t where);
+
+/* One clock tick of every co-resident group: everything a running deployment
+ * does at time `now`, per group and in this order.
+ *  A. ticker: every replica whose election timer is due is reset and, when it
+ *     is not Leader, is a candidate of this step; a Leader whose heartbeat
+ *     timer is due has fired (its reset comes in C); a non-leader's due
+ *     heartbeat timer is reset.
+ *  B. one election round: mraft_election_rounds with rounds = 1 and A's
+ *     candidates (state, flags and persist bits identical). A voter that
+ *     granted another replica's RequestVote gets an election reset
+ *     (raft_election.go:72); a replica that became Leader gets a heartbeat
+ *     reset (:39) and sends at once (:40).
+ *  C. sender: among the replicas that are Leader after B and fired in A,
+ *     became Leader in B, or (with MRAFT_CLOCK_SEND_ALL, for entries the host
+ *     Started between steps) simply hold office, the one with the highest
+ *     currentTerm, the lowest peer on a tie: leader_peer[g], or -1. Its
+ *     heartbeat timer is reset; a Leader that fired but was not chosen keeps
+ *     its due timer and fires again next step.
+ *  D. mraft_replicate_tick_export with that leader_peer, under the handle's
+ *     tick mode and shards.
+ *  E. in a group with MRAFT_G_ACTIVE and without MRAFT_G_ERROR: every replica
+ *     other than the sender whose currentTerm now equals the sender's term
+ *     before the tick gets an election reset (it passed the term gate of
+ *     raft_append_entry.go:121 / raft_snapshot.go:30; a follower's term after
+ *     handling is the larger of the two); with MRAFT_G_STEPPED_DOWN the
+ *     sender gets one (raft_append_entry.go:71, raft_snapshot.go:63). Groups
+ *     flagged MRAFT_G_LOG_FULL or MRAFT_G_FOLLOWER_PANIC follow the same rule.
+ * Outputs, each optional, one element per group: cand_mask (uint8, A's
+ * candidates as peer bits), leader_peer, election_flags (B's
+ * MRAFT_G_ELECTED / MRAFT_G_STEPPED_DOWN), group_flags / commit /
+ * term_leader (D's outputs). With MRAFT_DEVICE the call only enqueues work;
+ * with MRAFT_HOST it is synchronous. */
+enum { MRAFT_CLOCK_SEND_ALL = 1 };
+int mraft_clock_step(mraft_engine *h, int32_t now, uint32_t flags, uint8_t *cand_mask,
+                     int32_t *leader_peer, int32_t *election_flags, int32_t *group_flags,
+                     int32_t *commit, int32_t *term_leader, int32_t where);
+
 /* ---- persistence (raft.go:205-235, persister.go) ------------------------- */
 
 /* out_bits[slot] = persist_dirty[slot] for all G*P slots, then clears them:

@@ -14,7 +14,8 @@ from ._abi import (CANDIDATE, DEVICE, FOLLOWER, HOST, LEADER, TICK_AUTO, TICK_FU
 from .engine import (Engine, MraftError, copy_state, decode_persistent, entry_positions,  # noqa: F401
                      encode_persistent, new_state, state_sizes, synth_election_state,
                      synth_fold_batch, synth_tick_state)
+from .router import features, timer_draw  # noqa: F401
 
 __all__ = ["Engine", "MraftError", "new_state", "copy_state", "state_sizes", "synth_tick_state",
            "synth_fold_batch", "synth_election_state", "encode_persistent", "decode_persistent", "synth_seed", "LEADER", "CANDIDATE", "FOLLOWER", "HOST", "DEVICE",
-           "TICK_FULL", "TICK_LIGHT", "TICK_AUTO"]
+           "TICK_FULL", "TICK_LIGHT", "TICK_AUTO", "features", "timer_draw"]

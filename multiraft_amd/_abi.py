@@ -36,6 +36,10 @@ ABI_VERSION = 6
 FANIN_OVERLAP = 1
 FANIN_ORDERED = 2
 COMM_ID_BYTES = 128
+FEATURE_TIMERS = 1  # mraft_features
+(NOTE_AE_HANDLED, NOTE_IS_HANDLED, NOTE_RV_HANDLED, NOTE_AE_FOLDED, NOTE_IS_FOLDED,
+ NOTE_RV_FOLDED) = range(6)  # mraft_timers_note kinds
+CLOCK_SEND_ALL = 1
 SYN_MATCH, SYN_MISMATCH, SYN_BEYOND, SYN_STALE, SYN_BELOW_DUMMY, SYN_HEARTBEAT = range(6)
 
 
@@ -53,6 +57,15 @@ STATE_FIELDS = ("current_term", "voted_for", "state", "commit_index", "last_appl
 
 class MraftSoa(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in STATE_FIELDS]
+
+
+class MraftTimersSoa(ctypes.Structure):
+    _fields_ = [("election_due", ctypes.c_void_p), ("heartbeat_due", ctypes.c_void_p)]
+
+
+class MraftTimerConfig(ctypes.Structure):
+    _fields_ = [("seed", ctypes.c_uint32), ("heartbeat", ctypes.c_int32),
+                ("election_lo", ctypes.c_int32), ("election_hi", ctypes.c_int32)]
 
 
 AE_ARGS = np.dtype([("slot", "<i4"), ("term", "<i4"), ("leader_id", "<i4"),
@@ -101,6 +114,9 @@ ABI_SYMBOLS = (
     "mraft_set_tick_shards", "mraft_get_tick_shards", "mraft_shard_stream", "mraft_handle_append_entries_ex",
     "mraft_set_stage_capacity", "mraft_get_stage_capacity",
     "mraft_set_tick_mode", "mraft_get_tick_mode", "mraft_tick_light_fallbacks", "mraft_start_and_tick",
+    "mraft_features", "mraft_timer_draw", "mraft_timers_enable", "mraft_timers_disable",
+    "mraft_timers_load", "mraft_timers_store", "mraft_timers_arm", "mraft_ticker",
+    "mraft_timers_note", "mraft_clock_step",
 )
 SYNTH_SYMBOLS = ("mraft_synth_tick_state", "mraft_synth_fold_batch", "mraft_synth_election_state")
 
@@ -160,6 +176,16 @@ _SIGS = {
     "mraft_get_tick_mode": (_i32, [_vp]),
     "mraft_tick_light_fallbacks": (_i64, [_vp]),
     "mraft_start_and_tick": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "mraft_features": (_i32, []),
+    "mraft_timer_draw": (_i32, [ctypes.POINTER(MraftTimerConfig), _i64, _i32]),
+    "mraft_timers_enable": (ctypes.c_int, [_vp, ctypes.POINTER(MraftTimerConfig), _i32]),
+    "mraft_timers_disable": (ctypes.c_int, [_vp]),
+    "mraft_timers_load": (ctypes.c_int, [_vp, ctypes.POINTER(MraftTimersSoa), _i32]),
+    "mraft_timers_store": (ctypes.c_int, [_vp, ctypes.POINTER(MraftTimersSoa), _i32]),
+    "mraft_timers_arm": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32]),
+    "mraft_ticker": (ctypes.c_int, [_vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i32]),
+    "mraft_timers_note": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32]),
+    "mraft_clock_step": (ctypes.c_int, [_vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
 }
 _SYNTH_SIGS = {
     "mraft_synth_tick_state": (ctypes.c_int, [ctypes.c_uint64, _i32, _i32, _i32, _i32, _i32,

@@ -18,6 +18,7 @@
 #include "../../include/mraft.h"
 #include "mraft_device.h"
 #include "mraft_internal.h"
+#include "mraft_timer_draw.h"
 
 constexpr int kMaxShards = 8;
 // Default capacity of the AppendEntries stage (mraft_set_stage_capacity): 16 MiB.
@@ -94,6 +95,10 @@ struct mraft_engine {
   unsigned *lite_cnt = nullptr;
   int lite_par[kMaxShards] = {};
   int auto_since[kMaxShards] = {};  // MRAFT_TICK_AUTO: full ticks since the last light one
+  // Timers (mraft_timers_enable): both deadline arrays or neither, with the
+  // configuration they were armed under
+  int32_t *tm_ed = nullptr, *tm_hd = nullptr;
+  mraft_timer_config tcfg{};
   std::vector<void *> scratch_ptr;
   std::vector<size_t> scratch_cap;
 };
@@ -536,7 +541,8 @@ int mraft_destroy(mraft_engine *h) {
   // stream-ordered buffers (alloc_async): freed on the engine stream, then waited for
   for (void *p : h->scratch_ptr)
     if (p) (void)hipFreeAsync(p, h->stream);
-  for (void *p : {(void *)h->claim, (void *)h->srcmark, (void *)h->ae_total, (void *)h->lite_list, (void *)h->lite_cnt})
+  for (void *p : {(void *)h->claim, (void *)h->srcmark, (void *)h->ae_total, (void *)h->lite_list, (void *)h->lite_cnt,
+                  (void *)h->tm_ed, (void *)h->tm_hd})
     if (p) (void)hipFreeAsync(p, h->stream);
   (void)hipStreamSynchronize(h->stream);
   if (h->fanin_own) (void)hipStreamSynchronize(h->fanin_own);
@@ -1115,6 +1121,199 @@ int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask, int32_t rou
   TRY(sg.map(cand_mask, (size_t)rounds * h->G, true, false, &m));
   TRY(sg.map(group_flags, sizeof(int32_t) * h->G, false, true, &gf));
   mraft::launch_election_rounds(dev_of(h), (const uint8_t *)m, rounds, (int32_t *)gf, h->stream);
+  return sg.finish();
+}
+
+// ---------------------------------------------------------------- timers
+
+}  // extern "C"
+
+namespace {
+
+// Scratch slots of the clock step and the ticker (Stage maps from slot 8 up,
+// the message path owns 14-20).
+constexpr size_t kScrClockLp = 24, kScrClockGf = 25, kScrClockCommit = 26, kScrClockTl = 27, kScrClockTg = 28,
+                 kScrTickerCnt = 29;
+
+int check_now(int32_t now) {
+  if (now < 0 || now > mraft::kTimerNowMax) return fail(MRAFT_E_INVAL, "now = %d outside [0, 2^30]", now);
+  return MRAFT_OK;
+}
+
+// Every timer call but enable: a usable handle (enter) with timers enabled.
+int enter_timers(mraft_engine *h) {
+  TRY(enter(h));
+  if (!h->tm_ed) return fail(MRAFT_E_NOSTATE, "timers are not enabled (mraft_timers_enable)");
+  return MRAFT_OK;
+}
+
+mraft::TimerDev timers_of(const mraft_engine *h) { return mraft::TimerDev{h->tm_ed, h->tm_hd, h->tcfg}; }
+
+}  // namespace
+
+extern "C" {
+
+int mraft_timers_enable(mraft_engine *h, const mraft_timer_config *cfg, int32_t now) {
+  TRY(enter(h));
+  if (!cfg) return fail(MRAFT_E_INVAL, "cfg is null");
+  if (!mraft::timer_config_ok(*cfg))
+    return fail(MRAFT_E_INVAL,
+                "bad timer configuration heartbeat=%d election=[%d, %d) (need 1 <= heartbeat < 2^30, "
+                "1 <= election_lo < election_hi <= 2^20)",
+                cfg->heartbeat, cfg->election_lo, cfg->election_hi);
+  TRY(check_now(now));
+  // The arrays reach the handle only when both allocations and the arming
+  // launch succeeded; until then they are locals, freed on failure. A second
+  // enable re-arms the arrays the handle already has.
+  void *ed = h->tm_ed, *hd = h->tm_hd;
+  const bool fresh = !h->tm_ed;
+  const size_t b = (size_t)gp_of(h) * sizeof(int32_t);
+  if (fresh) {
+    TRY(alloc_async(h, &ed, b, "election_due"));
+    const int rc = alloc_async(h, &hd, b, "heartbeat_due");
+    if (rc) {
+      (void)hipFreeAsync(ed, h->stream);
+      return rc;
+    }
+  }
+  mraft::launch_timers_arm_all(mraft::TimerDev{(int32_t *)ed, (int32_t *)hd, *cfg}, gp_of(h), now, h->stream);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    if (fresh) {
+      (void)hipFreeAsync(ed, h->stream);
+      (void)hipFreeAsync(hd, h->stream);
+    }
+    return fail(MRAFT_E_HIP, "arming the timers failed: %s", hipGetErrorString(e));
+  }
+  h->tm_ed = (int32_t *)ed;
+  h->tm_hd = (int32_t *)hd;
+  h->tcfg = *cfg;
+  return MRAFT_OK;
+}
+
+int mraft_timers_disable(mraft_engine *h) {
+  TRY(enter_timers(h));
+  for (int32_t **p : {&h->tm_ed, &h->tm_hd}) {
+    if (*p) (void)hipFreeAsync(*p, h->stream);  // after the work already enqueued
+    *p = nullptr;
+  }
+  return MRAFT_OK;
+}
+
+int mraft_timers_load(mraft_engine *h, const mraft_timers_soa *src, int32_t where) {
+  TRY(enter_timers(h));
+  if (!src) return fail(MRAFT_E_INVAL, "src is null");
+  const hipMemcpyKind k = where == MRAFT_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  const size_t b = (size_t)gp_of(h) * sizeof(int32_t);
+  if (src->election_due) HIP_TRY(hipMemcpyAsync(h->tm_ed, src->election_due, b, k, h->stream));
+  if (src->heartbeat_due) HIP_TRY(hipMemcpyAsync(h->tm_hd, src->heartbeat_due, b, k, h->stream));
+  if (where == MRAFT_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
+  return MRAFT_OK;
+}
+
+int mraft_timers_store(mraft_engine *h, const mraft_timers_soa *dst, int32_t where) {
+  TRY(enter_timers(h));
+  if (!dst) return fail(MRAFT_E_INVAL, "dst is null");
+  const hipMemcpyKind k = where == MRAFT_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const size_t b = (size_t)gp_of(h) * sizeof(int32_t);
+  if (dst->election_due) HIP_TRY(hipMemcpyAsync(dst->election_due, h->tm_ed, b, k, h->stream));
+  if (dst->heartbeat_due) HIP_TRY(hipMemcpyAsync(dst->heartbeat_due, h->tm_hd, b, k, h->stream));
+  if (where == MRAFT_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
+  return MRAFT_OK;
+}
+
+int mraft_timers_arm(mraft_engine *h, const int32_t *slots, int64_t n, int32_t now, int32_t where) {
+  TRY(enter_timers(h));
+  if (n < 0 || (n > 0 && !slots)) return fail(MRAFT_E_INVAL, "null argument");
+  TRY(check_now(now));
+  if (n == 0) return MRAFT_OK;
+  Stage sg(h, where);
+  void *s;
+  TRY(sg.map(slots, sizeof(int32_t) * (size_t)n, true, false, &s));
+  mraft::launch_timers_arm(timers_of(h), (const int32_t *)s, n, gp_of(h), now, h->stream);
+  return sg.finish();
+}
+
+int mraft_ticker(mraft_engine *h, int32_t now, int32_t *out_election_slots, int64_t cap_e, int64_t *out_n_e,
+                 int32_t *out_heartbeat_slots, int64_t cap_h, int64_t *out_n_h, int32_t where) {
+  TRY(enter_timers(h));
+  if (cap_e < 0 || cap_h < 0 || !out_n_e || !out_n_h || (cap_e > 0 && !out_election_slots) ||
+      (cap_h > 0 && !out_heartbeat_slots))
+    return fail(MRAFT_E_INVAL, "null argument");
+  TRY(check_now(now));
+  // no list is longer than G*P: a larger buffer is used up to that
+  cap_e = std::min<int64_t>(cap_e, gp_of(h));
+  cap_h = std::min<int64_t>(cap_h, gp_of(h));
+  Stage sg(h, where);
+  void *oe, *oh, *ne, *nh, *bc;
+  TRY(sg.map(cap_e ? out_election_slots : nullptr, sizeof(int32_t) * (size_t)cap_e, false, true, &oe));
+  TRY(sg.map(cap_h ? out_heartbeat_slots : nullptr, sizeof(int32_t) * (size_t)cap_h, false, true, &oh));
+  TRY(sg.map(out_n_e, sizeof(int64_t), false, true, &ne));
+  TRY(sg.map(out_n_h, sizeof(int64_t), false, true, &nh));
+  TRY(scratch(h, kScrTickerCnt, sizeof(int32_t) * 2 * (size_t)mraft::ticker_blocks(gp_of(h)), &bc));
+  mraft::launch_ticker(dev_of(h), timers_of(h), now, (int32_t *)bc, (int32_t *)oe, cap_e, (int64_t *)ne,
+                       (int32_t *)oh, cap_h, (int64_t *)nh, h->stream);
+  return sg.finish();
+}
+
+int mraft_timers_note(mraft_engine *h, int32_t kind, const void *records, const void *outcome,
+                      const int32_t *item_err, int64_t n, int32_t now, int32_t where) {
+  TRY(enter_timers(h));
+  size_t rb = 0, ob = sizeof(int32_t);
+  switch (kind) {
+    case MRAFT_NOTE_AE_HANDLED: rb = sizeof(mraft_ae_args); ob = sizeof(mraft_ae_reply); break;
+    case MRAFT_NOTE_IS_HANDLED: rb = sizeof(mraft_is_args); ob = sizeof(mraft_is_reply); break;
+    case MRAFT_NOTE_RV_HANDLED: rb = sizeof(mraft_rv_args); ob = sizeof(mraft_rv_reply); break;
+    case MRAFT_NOTE_AE_FOLDED: rb = sizeof(mraft_ae_result); break;
+    case MRAFT_NOTE_IS_FOLDED: rb = sizeof(mraft_is_result); break;
+    case MRAFT_NOTE_RV_FOLDED: rb = sizeof(mraft_rv_result); break;
+    default: return fail(MRAFT_E_INVAL, "note kind %d", kind);
+  }
+  if (n < 0 || (n > 0 && (!records || !outcome))) return fail(MRAFT_E_INVAL, "null argument");
+  TRY(check_now(now));
+  if (n == 0) return MRAFT_OK;
+  Stage sg(h, where);
+  void *r, *o, *e;
+  TRY(sg.map(records, rb * (size_t)n, true, false, &r));
+  TRY(sg.map(outcome, ob * (size_t)n, true, false, &o));
+  TRY(sg.map(item_err, sizeof(int32_t) * (size_t)n, true, false, &e));
+  mraft::launch_timers_note(timers_of(h), kind, r, o, (const int32_t *)e, n, gp_of(h), now, h->stream);
+  return sg.finish();
+}
+
+int mraft_clock_step(mraft_engine *h, int32_t now, uint32_t flags, uint8_t *cand_mask, int32_t *leader_peer,
+                     int32_t *election_flags, int32_t *group_flags, int32_t *commit, int32_t *term_leader,
+                     int32_t where) {
+  TRY(enter_timers(h));
+  if (flags & ~(uint32_t)MRAFT_CLOCK_SEND_ALL) return fail(MRAFT_E_INVAL, "unknown flags 0x%x", flags);
+  TRY(check_now(now));
+  Stage sg(h, where);
+  const size_t gb = sizeof(int32_t) * (size_t)h->G;
+  void *cm, *ef, *tg;
+  // the words one launch hands to the next live in the caller's buffer when
+  // there is one, in the engine's scratch otherwise
+  void *need[4];
+  int32_t *const outs[4] = {leader_peer, group_flags, commit, term_leader};
+  const size_t slots[4] = {kScrClockLp, kScrClockGf, kScrClockCommit, kScrClockTl};
+  for (int k = 0; k < 4; ++k) {
+    if (outs[k])
+      TRY(sg.map(outs[k], gb, false, true, &need[k]));
+    else
+      TRY(scratch(h, slots[k], gb, &need[k]));
+  }
+  TRY(sg.map(cand_mask, (size_t)h->G, false, true, &cm));
+  TRY(sg.map(election_flags, gb, false, true, &ef));
+  TRY(scratch(h, kScrClockTg, gb, &tg));
+  int32_t *lp = (int32_t *)need[0], *gf = (int32_t *)need[1];
+  const mraft::TimerDev t = timers_of(h);
+  // A-C: ticker, one election round, the sender
+  mraft::launch_clock_round(dev_of(h), t, now, flags, (uint8_t *)cm, lp, (int32_t *)tg, (int32_t *)ef, h->stream);
+  // D: the tick, under the handle's mode and shards
+  TRY(launch_tick(h, lp, gf, (int32_t *)need[2], (int32_t *)need[3]));
+  // E: the tick's resets, on the engine stream after every shard (a
+  // device-side wait)
+  TRY(join_shards(h));
+  mraft::launch_clock_resets(dev_of(h), t, now, gf, lp, (const int32_t *)tg, h->stream);
   return sg.finish();
 }
 

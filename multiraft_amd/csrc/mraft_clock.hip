@@ -1,0 +1,366 @@
+// mraft_clock.hip — the device-resident timers (include/mraft.h "timers") for
+// gfx950: ticker() (raft.go:106-125) over two deadline arrays in HBM, the
+// reference's seven timer-reset sites, and the clock step of co-resident
+// groups.
+//
+// The clock step's first launch (k_clock_round) uses the election storm's
+// layout (mraft_elect.hip): one lane per replica, eight lanes per group, so a
+// group's eight deadlines and roles are one segment's registers; the ticker
+// (A), one election round (B, the storm's round body included as text from
+// mraft_elect_round.inc) and the choice of the sender (C) run on them with
+// HBM touched once on entry and once on exit. The tick (D) is the existing
+// launch; k_clock_resets (E) follows it with the same layout.
+//
+// Occupancy: the kernels here declare __launch_bounds__(256) and nothing
+// more: the compiler's resource remarks give every kernel 8 waves per SIMD
+// with no scratch. k_clock_round<P> takes 35 (P = 1) to 64 (P = 8) VGPRs,
+// the last exactly the 64 that 8 waves per SIMD leave each, and 2,560 B of
+// LDS per workgroup (DESIGN.md §8d records the figures).
+#include "mraft_device.h"
+#include "mraft_internal.h"
+#include "mraft_timer_draw.h"
+
+namespace mraft {
+
+namespace {
+
+// "Election reset at now" / "heartbeat reset" (include/mraft.h).
+__device__ __forceinline__ int election_deadline(const TimerDev &t, int64_t slot, int now) {
+  return now + timer_draw(t.cfg, (uint32_t)slot, (uint32_t)now);
+}
+__device__ __forceinline__ int heartbeat_deadline(const TimerDev &t, int now) { return now + t.cfg.heartbeat; }
+
+// Make's two NewTimer calls (raft.go:66-67) for every slot.
+__global__ __launch_bounds__(256) void k_timers_arm_all(TimerDev t, int64_t gp, int now) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= gp) return;
+  t.ed[i] = election_deadline(t, i, now);
+  t.hd[i] = heartbeat_deadline(t, now);
+}
+
+// ... and for the listed slots (restarted replicas); out-of-range slots skipped.
+__global__ __launch_bounds__(256) void k_timers_arm(TimerDev t, const int32_t *__restrict__ slots, int64_t n,
+                                                    int64_t gp, int now) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t sl = slots[i];
+  if (sl < 0 || sl >= gp) return;
+  t.ed[sl] = election_deadline(t, sl, now);
+  t.hd[sl] = heartbeat_deadline(t, now);
+}
+
+// ---------------------------------------------------------------- ticker
+// ticker() for every slot, the two lists compacted in ascending slot order in
+// three launches (per-block counts, one-workgroup exclusive scan per list,
+// emit), as the compacted applier does (mraft_kernels.hip).
+struct TickerLane {
+  bool edue, hdue, leader;
+};
+
+__device__ __forceinline__ TickerLane ticker_lane(const Dev &s, const TimerDev &t, int64_t i, int64_t gp,
+                                                  int now) {
+  TickerLane l{false, false, false};
+  if (i < gp) {
+    l.edue = t.ed[i] <= now;
+    l.hdue = t.hd[i] <= now;
+    l.leader = s.role[i] == kLeader;
+  }
+  return l;
+}
+
+__global__ __launch_bounds__(256) void k_ticker_count(Dev s, TimerDev t, int now, int32_t *__restrict__ bcnt,
+                                                      int64_t nb) {
+  const int64_t gp = (int64_t)s.G * s.P;
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const TickerLane l = ticker_lane(s, t, i, gp, now);
+  const unsigned long long me = __ballot(l.edue && !l.leader);          // raft.go:112-114
+  const unsigned long long mh = __ballot(l.hdue && l.leader);           // :119-121
+  __shared__ int wc[2][4];
+  if (lane_id() == 0) {
+    wc[0][threadIdx.x >> 6] = __popcll(me);
+    wc[1][threadIdx.x >> 6] = __popcll(mh);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int k = threadIdx.x;
+    bcnt[k * nb + blockIdx.x] = wc[k][0] + wc[k][1] + wc[k][2] + wc[k][3];
+  }
+}
+
+// Workgroup k scans list k's block counts in place (exclusive), 1,024 at a
+// time with a carry, and writes the list's total.
+__global__ __launch_bounds__(1024) void k_ticker_scan(int32_t *__restrict__ bcnt, int64_t nb,
+                                                      int64_t *__restrict__ total_e,
+                                                      int64_t *__restrict__ total_h) {
+  __shared__ int64_t part[1024];
+  int32_t *c = bcnt + blockIdx.x * nb;
+  int64_t carry = 0;
+  for (int64_t base = 0; base < nb; base += 1024) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t v = i < nb ? c[i] : 0;
+    part[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {  // inclusive Hillis-Steele scan
+      const int64_t add = threadIdx.x >= (unsigned)o ? part[threadIdx.x - o] : 0;
+      __syncthreads();
+      part[threadIdx.x] += add;
+      __syncthreads();
+    }
+    if (i < nb) c[i] = (int32_t)(carry + part[threadIdx.x] - v);
+    const int64_t chunk = part[1023];
+    __syncthreads();
+    carry += chunk;
+  }
+  if (threadIdx.x == 0) *(blockIdx.x == 0 ? total_e : total_h) = carry;
+}
+
+__global__ __launch_bounds__(256) void k_ticker_emit(Dev s, TimerDev t, int now, const int32_t *__restrict__ boff,
+                                                     int64_t nb, int64_t cap_e, int64_t cap_h,
+                                                     int32_t *__restrict__ oe, int32_t *__restrict__ oh) {
+  const int64_t gp = (int64_t)s.G * s.P;
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const TickerLane l = ticker_lane(s, t, i, gp, now);
+  const bool le = l.edue && !l.leader, lh = l.hdue && l.leader;
+  const unsigned long long me = __ballot(le), mh = __ballot(lh);
+  __shared__ int wc[2][4];
+  if (lane_id() == 0) {
+    wc[0][threadIdx.x >> 6] = __popcll(me);
+    wc[1][threadIdx.x >> 6] = __popcll(mh);
+  }
+  __syncthreads();
+  const int w = threadIdx.x >> 6;
+  int64_t offe = boff[blockIdx.x], offh = boff[nb + blockIdx.x];
+  for (int k = 0; k < w; ++k) {
+    offe += wc[0][k];
+    offh += wc[1][k];
+  }
+  const unsigned long long below = (1ull << lane_id()) - 1;
+  offe += __popcll(me & below);
+  offh += __popcll(mh & below);
+  // A listed slot whose entry does not fit keeps its due timer (the caller
+  // calls again for the rest); every other due timer is reset (:111, :118).
+  if (l.edue) {
+    const bool fits = offe < cap_e;
+    if (le && fits) oe[offe] = (int32_t)i;
+    if (!le || fits) t.ed[i] = election_deadline(t, i, now);
+  }
+  if (l.hdue) {
+    const bool fits = offh < cap_h;
+    if (lh && fits) oh[offh] = (int32_t)i;
+    if (!lh || fits) t.hd[i] = heartbeat_deadline(t, now);
+  }
+}
+
+// ---------------------------------------------------------------- reset sites
+// The resets that follow a message-path call, from the arrays it returned
+// (include/mraft.h mraft_timers_note): one lane per item. Items that repeat a
+// slot write the same deadline (the draw depends on slot and now only).
+__global__ __launch_bounds__(256) void k_timers_note(TimerDev t, int kind, const void *__restrict__ records,
+                                                     const void *__restrict__ outcome,
+                                                     const int32_t *__restrict__ item_err, int64_t n,
+                                                     int64_t gp, int now) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (item_err && item_err[i] != 0) return;
+  int64_t slot = -1;
+  bool hit = false;
+  switch (kind) {
+    case MRAFT_NOTE_AE_HANDLED: {                                      // raft_append_entry.go:121
+      const mraft_ae_args *a = (const mraft_ae_args *)records + i;
+      slot = a->slot;
+      hit = ((const mraft_ae_reply *)outcome)[i].term <= a->term;
+      break;
+    }
+    case MRAFT_NOTE_IS_HANDLED: {                                      // raft_snapshot.go:30
+      const mraft_is_args *a = (const mraft_is_args *)records + i;
+      slot = a->slot;
+      hit = ((const mraft_is_reply *)outcome)[i].term <= a->term;
+      break;
+    }
+    case MRAFT_NOTE_RV_HANDLED:                                        // raft_election.go:72
+      slot = ((const mraft_rv_args *)records)[i].slot;
+      hit = ((const mraft_rv_reply *)outcome)[i].vote_granted != 0;
+      break;
+    case MRAFT_NOTE_AE_FOLDED:                                         // raft_append_entry.go:71
+      slot = ((const mraft_ae_result *)records)[i].slot;
+      hit = (((const int32_t *)outcome)[i] & MRAFT_F_STEPPED_DOWN) != 0;
+      break;
+    case MRAFT_NOTE_IS_FOLDED:                                         // raft_snapshot.go:63
+      slot = ((const mraft_is_result *)records)[i].slot;
+      hit = (((const int32_t *)outcome)[i] & MRAFT_F_STEPPED_DOWN) != 0;
+      break;
+    case MRAFT_NOTE_RV_FOLDED:                                         // raft_election.go:39
+      slot = ((const mraft_rv_result *)records)[i].slot;
+      hit = (((const int32_t *)outcome)[i] & MRAFT_F_BECAME_LEADER) != 0;
+      break;
+    default: break;
+  }
+  if (!hit || slot < 0 || slot >= gp) return;
+  if (kind == MRAFT_NOTE_RV_FOLDED)
+    t.hd[slot] = heartbeat_deadline(t, now);
+  else
+    t.ed[slot] = election_deadline(t, slot, now);
+}
+
+// ---------------------------------------------------------------- clock step
+// A (ticker), B (one election round) and C (the sender) of mraft_clock_step
+// for eight groups per wave. The state registers, the LDS words and the round
+// body are k_election_rounds' (mraft_elect.hip); this kernel adds the two
+// deadlines per lane, the per-voter grant (gm, left in scope by the round
+// body) and the sender's choice by segment shuffles.
+template <int P>
+__global__ __launch_bounds__(256) void k_clock_round(Dev s, TimerDev t, int now, unsigned flags,
+                                                     uint8_t *__restrict__ cand, int32_t *__restrict__ lpeer,
+                                                     int32_t *__restrict__ tg, int32_t *__restrict__ gflags) {
+  const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int g = tid >> 3, p = tid & 7;
+  const bool grp = g < s.G;  // uniform over the segment
+  const bool act = grp && p < P;
+  const long long sl = (long long)g * P + p;
+  int term = 0, voted = -1, role = kFollower, votes = 0, last = 0, lterm = 0;
+  int ed = INT32_MAX, hd = INT32_MAX;
+  if (act) {
+    term = s.term[sl];
+    voted = s.voted[sl];
+    role = s.role[sl];
+    votes = s.votes[sl];
+    last = s.last[sl];
+    lterm = term_at(s, sl, s.dummy[sl], s.head[sl], last);             // lastEntry, raft_log.go:50-53
+    ed = t.ed[sl];
+    hd = t.hd[sl];
+  }
+  constexpr int kVJunk = 0x100;  // votedFor outside [-1, P): as in k_election_rounds
+  const int pb = 1 << p;
+  int vb = voted == -1 ? 0 : ((unsigned)voted < (unsigned)P ? 1 << voted : kVJunk);
+  int upm = 0;  // bit c: candidate c's log is up to date for this voter (raft_log.go:99-104)
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    const int clt = __shfl(lterm, c, 8), clast = __shfl(last, c, 8);
+    upm |= (int)(clt > lterm || (clt == lterm && clast >= last)) << c;
+  }
+  __shared__ int lds_cx[256];
+  __shared__ __attribute__((aligned(8))) uint8_t lds_gm[256];
+  __shared__ int lds_rt[256];
+  __shared__ __attribute__((aligned(8))) uint8_t lds_rc[256];
+  const int seg = (int)(threadIdx.x & 63) & ~7;
+  int fl = 0, became = 0, pd = 0;
+
+  // A. ticker (raft.go:106-125). Every reset of this replica in this step
+  // happens at `now`, so they all set the same deadline.
+  const int ed_new = act ? election_deadline(t, sl, now) : 0;
+  const int hd_new = heartbeat_deadline(t, now);
+  const bool edue = act && ed <= now, hdue = act && hd <= now;
+  ed = edue ? ed_new : ed;                                             // :111
+  const bool fired = hdue && role == kLeader;                          // :119-121; its reset comes in C
+  hd = (hdue && role != kLeader) ? hd_new : hd;                        // :118
+  const int m = (int)((__ballot(edue) >> seg) & 0xffull);              // the round's timeouts (:112-114)
+
+  // B. one election round
+#include "mraft_elect_round.inc"
+  ed = (act && (gm & ~pb) != 0) ? ed_new : ed;                         // granted another replica, raft_election.go:72
+  hd = became ? hd_new : hd;                                           // :39
+
+  // C. the sender: highest currentTerm, lowest peer on a tie
+  const int elig = act && role == kLeader && (fired || became || (flags & MRAFT_CLOCK_SEND_ALL));
+  int bp = -1, bt = 0;
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    const int ce = __shfl(elig, c, 8), ct = __shfl(term, c, 8);
+    const bool take = ce && (bp < 0 || ct > bt);
+    bt = take ? ct : bt;
+    bp = take ? c : bp;
+  }
+  hd = (act && p == bp) ? hd_new : hd;
+
+  const unsigned long long el = __ballot(fl & MRAFT_G_ELECTED), sd = __ballot(fl & MRAFT_G_STEPPED_DOWN);
+  if (grp && p == 0) {
+    if (cand) cand[g] = (uint8_t)cm;
+    lpeer[g] = bp;
+    tg[g] = bt;
+    if (gflags)
+      gflags[g] = (((el >> seg) & 0xffull) ? MRAFT_G_ELECTED : 0) |
+                  (((sd >> seg) & 0xffull) ? MRAFT_G_STEPPED_DOWN : 0);
+  }
+  if (!act) return;
+  s.term[sl] = term;
+  s.voted[sl] = (vb & kVJunk) ? voted : (vb ? __builtin_ctz(vb) : -1);
+  s.role[sl] = role;
+  s.votes[sl] = votes;
+  t.ed[sl] = ed;
+  t.hd[sl] = hd;
+  if (pd) mark_persist(s, sl, MRAFT_PERSIST_STATE);
+  if (became) {
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      s.match[sl * P + j] = 0;
+      s.next[sl * P + j] = last + 1;
+    }
+  }
+}
+
+// E. the resets of the tick, from its group flags and the terms it left: a
+// follower whose term equals the sender's pre-tick term passed the term gate
+// of its handler (raft_append_entry.go:121, raft_snapshot.go:30); a sender
+// that stepped down reset its own timer (:71, raft_snapshot.go:63).
+__global__ __launch_bounds__(256) void k_clock_resets(Dev s, TimerDev t, int now,
+                                                      const int32_t *__restrict__ gflags,
+                                                      const int32_t *__restrict__ lpeer,
+                                                      const int32_t *__restrict__ tg) {
+  const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int g = tid >> 3, p = tid & 7;
+  if (g >= s.G || p >= s.P) return;
+  const int gf = gflags[g];
+  if (!(gf & MRAFT_G_ACTIVE) || (gf & MRAFT_G_ERROR)) return;
+  const long long sl = (long long)g * s.P + p;
+  const bool hit = p != lpeer[g] ? s.term[sl] == tg[g] : (gf & MRAFT_G_STEPPED_DOWN) != 0;
+  if (hit) t.ed[sl] = election_deadline(t, sl, now);
+}
+
+unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+void launch_timers_arm_all(const TimerDev &t, int64_t gp, int32_t now, hipStream_t st) {
+  hipLaunchKernelGGL(k_timers_arm_all, dim3(blocks256(gp)), dim3(256), 0, st, t, gp, now);
+}
+
+void launch_timers_arm(const TimerDev &t, const int32_t *slots, int64_t n, int64_t gp, int32_t now,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(k_timers_arm, dim3(blocks256(n)), dim3(256), 0, st, t, slots, n, gp, now);
+}
+
+void launch_ticker(const Dev &s, const TimerDev &t, int32_t now, int32_t *bcnt, int32_t *oe, int64_t cap_e,
+                   int64_t *n_e, int32_t *oh, int64_t cap_h, int64_t *n_h, hipStream_t st) {
+  const int64_t nb = ticker_blocks((int64_t)s.G * s.P);
+  hipLaunchKernelGGL(k_ticker_count, dim3((unsigned)nb), dim3(256), 0, st, s, t, now, bcnt, nb);
+  hipLaunchKernelGGL(k_ticker_scan, dim3(2), dim3(1024), 0, st, bcnt, nb, n_e, n_h);
+  hipLaunchKernelGGL(k_ticker_emit, dim3((unsigned)nb), dim3(256), 0, st, s, t, now, bcnt, nb, cap_e, cap_h, oe,
+                     oh);
+}
+
+void launch_timers_note(const TimerDev &t, int kind, const void *records, const void *outcome,
+                        const int32_t *item_err, int64_t n, int64_t gp, int32_t now, hipStream_t st) {
+  hipLaunchKernelGGL(k_timers_note, dim3(blocks256(n)), dim3(256), 0, st, t, kind, records, outcome, item_err, n,
+                     gp, now);
+}
+
+void launch_clock_round(const Dev &s, const TimerDev &t, int32_t now, uint32_t flags, uint8_t *cand,
+                        int32_t *lpeer, int32_t *tg, int32_t *eflags, hipStream_t st) {
+  const dim3 gr(blocks256((int64_t)s.G * 8)), bl(256);
+  switch (s.P) {
+#define MRAFT_CK_CASE(PP) \
+  case PP: hipLaunchKernelGGL(k_clock_round<PP>, gr, bl, 0, st, s, t, now, flags, cand, lpeer, tg, eflags); break;
+    MRAFT_CK_CASE(1) MRAFT_CK_CASE(2) MRAFT_CK_CASE(3) MRAFT_CK_CASE(4)
+    MRAFT_CK_CASE(5) MRAFT_CK_CASE(6) MRAFT_CK_CASE(7) MRAFT_CK_CASE(8)
+#undef MRAFT_CK_CASE
+    default: break;
+  }
+}
+
+void launch_clock_resets(const Dev &s, const TimerDev &t, int32_t now, const int32_t *gflags,
+                         const int32_t *lpeer, const int32_t *tg, hipStream_t st) {
+  hipLaunchKernelGGL(k_clock_resets, dim3(blocks256((int64_t)s.G * 8)), dim3(256), 0, st, s, t, now, gflags, lpeer,
+                     tg);
+}
+
+}  // namespace mraft

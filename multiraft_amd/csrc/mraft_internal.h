@@ -129,6 +129,29 @@ void launch_tally(const Dev &s, const mraft_rv_result *items, int64_t n, const i
                   hipStream_t st);
 void launch_election_rounds(const Dev &s, const uint8_t *cand, int R, int32_t *gflags,
                             hipStream_t st);
+// Timers (mraft_clock.hip; include/mraft.h "timers"): the two deadline arrays
+// of a handle with its configuration.
+struct TimerDev {
+  int32_t *ed, *hd;  // election_due, heartbeat_due [G*P]
+  mraft_timer_config cfg;
+};
+void launch_timers_arm_all(const TimerDev &t, int64_t gp, int32_t now, hipStream_t st);
+void launch_timers_arm(const TimerDev &t, const int32_t *slots, int64_t n, int64_t gp, int32_t now,
+                       hipStream_t st);
+// mraft_ticker: count / scan / emit (as launch_collect_apply_compact). bcnt
+// holds 2 * ticker_blocks(gp) words: the election list's block counts, then
+// the heartbeat list's.
+inline int64_t ticker_blocks(int64_t gp) { return (gp + 255) / 256; }
+void launch_ticker(const Dev &s, const TimerDev &t, int32_t now, int32_t *bcnt, int32_t *oe, int64_t cap_e,
+                   int64_t *n_e, int32_t *oh, int64_t cap_h, int64_t *n_h, hipStream_t st);
+void launch_timers_note(const TimerDev &t, int kind, const void *records, const void *outcome,
+                        const int32_t *item_err, int64_t n, int64_t gp, int32_t now, hipStream_t st);
+// mraft_clock_step A-C (ticker, one election round, the sender; lpeer and tg,
+// the sender's term, are required) and E (the tick's resets).
+void launch_clock_round(const Dev &s, const TimerDev &t, int32_t now, uint32_t flags, uint8_t *cand,
+                        int32_t *lpeer, int32_t *tg, int32_t *eflags, hipStream_t st);
+void launch_clock_resets(const Dev &s, const TimerDev &t, int32_t now, const int32_t *gflags,
+                         const int32_t *lpeer, const int32_t *tg, hipStream_t st);
 void launch_collect_persist(const Dev &s, int32_t *out, hipStream_t st);
 void launch_read_persistent_hdr(const Dev &s, const int32_t *slots, int64_t n,
                                 mraft_persistent *out, hipStream_t st);

@@ -431,6 +431,84 @@ class Engine:
             "mraft_election_rounds")
         return group_flags
 
+    # ---- timers (ticker, raft.go:106-125) --------------------------------
+    def timers_enable(self, seed: int, heartbeat: int, election_lo: int, election_hi: int, now: int = 0):
+        """Device-resident election / heartbeat deadlines for every slot, armed
+        at `now` (mraft_timers_enable; again: re-arms with the new configuration)."""
+        cfg = _abi.MraftTimerConfig(seed & 0xFFFFFFFF, heartbeat, election_lo, election_hi)
+        _ck(self._lib.mraft_timers_enable(self._h, ctypes.byref(cfg), now), "mraft_timers_enable")
+
+    def timers_disable(self):
+        _ck(self._lib.mraft_timers_disable(self._h), "mraft_timers_disable")
+
+    def timers_load(self, election_due=None, heartbeat_due=None, where: int = HOST):
+        if where == HOST:
+            election_due = None if election_due is None else np.ascontiguousarray(election_due, dtype=np.int32)
+            heartbeat_due = None if heartbeat_due is None else np.ascontiguousarray(heartbeat_due, dtype=np.int32)
+        soa = _abi.MraftTimersSoa(ptr(election_due), ptr(heartbeat_due))
+        _ck(self._lib.mraft_timers_load(self._h, ctypes.byref(soa), where), "mraft_timers_load")
+
+    def timers_store(self):
+        """(election_due, heartbeat_due) as host arrays."""
+        ed = np.empty(self.G * self.P, np.int32)
+        hd = np.empty(self.G * self.P, np.int32)
+        soa = _abi.MraftTimersSoa(ptr(ed), ptr(hd))
+        _ck(self._lib.mraft_timers_store(self._h, ctypes.byref(soa), HOST), "mraft_timers_store")
+        return ed, hd
+
+    def timers_arm(self, slots, now: int, where: int = HOST):
+        """Both timers of restarted replicas (after `restore`), as Make arms them."""
+        if where == HOST:
+            slots = np.ascontiguousarray(slots, dtype=np.int32)
+        _ck(self._lib.mraft_timers_arm(self._h, ptr(slots), len(slots), now, where), "mraft_timers_arm")
+
+    def ticker(self, now: int, cap_e: int | None = None, cap_h: int | None = None):
+        """ticker() for every slot: (election_slots, n_e, heartbeat_slots, n_h)
+        — the non-leaders that timed out (for `start_election`) and the
+        leaders whose heartbeat fired (for `gather_append_args`), ascending;
+        n_* are the full counts, the arrays hold the first min(n, cap) and
+        only those had their timers reset."""
+        gp = self.G * self.P
+        cap_e = gp if cap_e is None else cap_e
+        cap_h = gp if cap_h is None else cap_h
+        oe, oh = np.zeros(max(cap_e, 1), np.int32), np.zeros(max(cap_h, 1), np.int32)
+        ne, nh = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        _ck(self._lib.mraft_ticker(self._h, now, ptr(oe) if cap_e else None, cap_e, ptr(ne),
+                                   ptr(oh) if cap_h else None, cap_h, ptr(nh), HOST), "mraft_ticker")
+        ke, kh = int(min(ne[0], cap_e)), int(min(nh[0], cap_h))
+        return oe[:ke].copy(), int(ne[0]), oh[:kh].copy(), int(nh[0])
+
+    _NOTE_DTYPES = {_abi.NOTE_AE_HANDLED: (AE_ARGS, AE_REPLY), _abi.NOTE_IS_HANDLED: (IS_ARGS, IS_REPLY),
+                    _abi.NOTE_RV_HANDLED: (RV_ARGS, RV_REPLY), _abi.NOTE_AE_FOLDED: (AE_RESULT, np.int32),
+                    _abi.NOTE_IS_FOLDED: (IS_RESULT, np.int32), _abi.NOTE_RV_FOLDED: (RV_RESULT, np.int32)}
+
+    def timers_note(self, kind: int, records, outcome, item_err, now: int, where: int = HOST):
+        """The reference's timer resets after a message-path call, from the
+        arrays that call returned (mraft_timers_note; kinds _abi.NOTE_*)."""
+        if where == HOST:
+            rd, od = self._NOTE_DTYPES[kind]
+            records = np.ascontiguousarray(records, dtype=rd)
+            outcome = np.ascontiguousarray(outcome, dtype=od)
+            item_err = None if item_err is None else np.ascontiguousarray(item_err, dtype=np.int32)
+        _ck(self._lib.mraft_timers_note(self._h, kind, ptr(records), ptr(outcome), ptr(item_err),
+                                        len(records), now, where), "mraft_timers_note")
+
+    def clock_step(self, now: int, send_all: bool = False, where: int = HOST, out: dict | None = None):
+        """One clock tick of every group (mraft_clock_step): timeouts, one
+        election round, heartbeats and replication. Host arrays: returns a
+        dict of cand_mask (uint8), leader_peer, election_flags, group_flags,
+        commit and term_leader, one element per group. With where=DEVICE,
+        `out` holds the device tensors to fill (any subset) and the call only
+        enqueues work."""
+        names = ("cand_mask", "leader_peer", "election_flags", "group_flags", "commit", "term_leader")
+        if where == HOST:
+            out = {n: np.zeros(self.G, np.uint8 if n == "cand_mask" else np.int32) for n in names}
+        else:
+            out = out or {}
+        _ck(self._lib.mraft_clock_step(self._h, now, _abi.CLOCK_SEND_ALL if send_all else 0,
+                                       *(ptr(out.get(n)) for n in names), where), "mraft_clock_step")
+        return out
+
     # ---- persistence (raft.go:205-235) ------------------------------------
     def collect_persist(self):
         """persist_dirty of every slot (MRAFT_PERSIST_* bits), cleared on read."""

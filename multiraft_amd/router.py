@@ -36,6 +36,21 @@ def key2shard(key, nshards: int = NSHARDS) -> int:
     return r
 
 
+def features() -> int:
+    """mraft_features: the library's optional capabilities (_abi.FEATURE_*)."""
+    return int(_abi.lib().mraft_features())
+
+
+def timer_draw(seed: int, slot: int, now: int, election_lo: int, election_hi: int, heartbeat: int = 1) -> int:
+    """mraft_timer_draw (host code): the election timeout a reset of replica
+    `slot` at time `now` draws, in [election_lo, election_hi)."""
+    cfg = _abi.MraftTimerConfig(seed & 0xFFFFFFFF, heartbeat, election_lo, election_hi)
+    r = int(_abi.lib().mraft_timer_draw(ctypes.byref(cfg), slot, now))
+    if r < 0:
+        raise ValueError("bad timer configuration, slot or now")
+    return r
+
+
 def realloc_gid(shards, gids):
     """Config.ReAllocGID (common.go:87-132) on a copy: the new shard -> gid array."""
     sh = np.ascontiguousarray(shards, dtype=np.int32).copy()
