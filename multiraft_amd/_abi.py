@@ -27,6 +27,7 @@ OK, E_INVAL, E_NOMEM, E_HIP, E_NOSTATE = 0, -1, -2, -3, -4
 F_NEED_MORE, F_COMMITTED, F_STEPPED_DOWN, F_BECAME_LEADER, F_APPLIED = 1, 2, 4, 8, 16
 F_SNAPSHOT_INSTALLED = 32
 G_SNAPSHOT_INSTALLED = 256
+G_FOLLOWER_PANIC = 512
 (G_ACTIVE, G_COMMITTED, G_STEPPED_DOWN, G_NEED_SNAPSHOT, G_ERROR, G_FOLLOWER_COMMIT,
  G_LOG_FULL, G_ELECTED) = 1, 2, 4, 8, 16, 32, 64, 128
 PERSIST_STATE, PERSIST_SNAPSHOT = 1, 2

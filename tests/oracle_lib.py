@@ -86,6 +86,14 @@ class Oracle:
     def state(self) -> dict:
         return self.st
 
+    def load_state(self, st: dict):
+        """Replace the whole state in place, as mraft_load_state does
+        (terms_sorted recomputed from the logs)."""
+        for k, v in self.st.items():
+            if k != "terms_sorted":
+                v[:] = st[k]
+        lib().ora_compute_terms_sorted(ctypes.byref(self._e))
+
     def replicate_tick(self, leader_peer, nthreads: int = 1):
         lp = np.ascontiguousarray(leader_peer, dtype=np.int32)
         gf = np.zeros(self.G, dtype=np.int32)

@@ -3,8 +3,10 @@ through the C ABI: enable / arm / load / store, mraft_ticker (counts, caps and
 remainders), mraft_timers_note for the six reset sites on real outputs of the
 message path, mraft_clock_step on arbitrary states, and the self-driving run
 (test_test.go TestInitialElection / TestReElection). After every call the
-whole state and both timer arrays equal the model's. No test asserts a tick
-mode: they pass under every one."""
+whole state and both timer arrays equal the model's. The tests of sections
+1-3 and the CLOCK_CASES assert no tick mode and pass under every one; the
+clock step also runs under each mode set by the test, with 1, 2 and 3 tick
+shards (section 4b), and the self-driving run under MRAFT_TICK_LIGHT."""
 import ctypes
 
 import numpy as np
@@ -13,10 +15,10 @@ import pytest
 from message_cases import all_follower_items, external_entries, results_of
 from oracle_lib import assert_states_equal
 from random_states import random_tick_state
-from timers_cases import CFG, CLOCK_CASES, CLOCK_STEPS, NOW0, clock_case_model, due_timers
+from timers_cases import CFG, CLOCK_CASES, CLOCK_STEPS, NOW0, clock_case_model, due_timers, leaders_in_place_state
 from timers_model import SELF_CFG, SELF_L, SELF_SHAPES, ModelNode, TimersModel, self_driving
 
-from multiraft_amd import Engine, _abi, new_state, synth_election_state
+from multiraft_amd import Engine, _abi, new_state
 from multiraft_amd._abi import (HOST, IS_RESULT, LEADER, NOTE_AE_FOLDED, NOTE_AE_HANDLED, NOTE_IS_FOLDED,
                                 NOTE_IS_HANDLED, NOTE_RV_FOLDED, NOTE_RV_HANDLED, RV_ARGS, RV_RESULT, ptr)
 
@@ -112,13 +114,7 @@ def test_enable_arm_load_store(G, P, L):
 def test_ticker(G, P, L):
     rng = np.random.default_rng(100 + G)
     gp = G * P
-    st, _ = synth_election_state(G, P, L, seed=700 + G, rounds=1)
-    if P > 1:  # leaders in place
-        lead = rng.random(G) < 0.7
-        sl = np.nonzero(lead)[0] * P + rng.integers(0, P, int(lead.sum()))
-        st["state"][sl] = LEADER
-    else:
-        st["state"][rng.random(gp) < 0.5] = LEADER
+    st = leaders_in_place_state(G, P, L, rng, seed=700 + G)
     m = TimersModel(G, P, L, st)
     now = 500
     with Engine(G, P, L) as e:
@@ -135,18 +131,30 @@ def test_ticker(G, P, L):
             return got
 
         for share in (0.0, 0.5, 1.0):
-            load_both(e, m, due_timers(rng, gp, now, share), due_timers(rng, gp, now, share))
-            _, ne, _, nh = tick(now, 0, 0, f"share {share}, cap 0")
-            # nothing was written, so every listed slot is still due; one less than fits ...
-            ce, ch = max(ne - 1, 0), max(nh - 1, 0)
-            e1, ne1, h1, nh1 = tick(now, ce, ch, f"share {share}, cap n - 1")
-            assert (ne1, nh1, len(e1), len(h1)) == (ne, nh, ce, ch)
-            # ... and the second call returns the remainder
-            e2, ne2, h2, nh2 = tick(now, gp, gp, f"share {share}, remainder")
-            assert (ne2, nh2) == (ne - ce, nh - ch) and len(e2) == ne2 and len(h2) == nh2
-            assert ne2 == 0 or e2[0] > (e1[-1] if len(e1) else -1)
-            assert tick(now, gp, gp, f"share {share}, nothing left")[1::2] == (0, 0)
-            now += 3
+            # capacities that cut the lists one short of full, after the first slot (mid-wave, in the first
+            # block) and in the middle (mid-block, and for 262,155 slots past the scan's first chunk)
+            for cut in ("n - 1", "1", "n // 2"):
+                load_both(e, m, due_timers(rng, gp, now, share), due_timers(rng, gp, now, share))
+                leader = st["state"] == LEADER
+                full_e, full_h = np.nonzero((m.ed <= now) & ~leader)[0], np.nonzero((m.hd <= now) & leader)[0]
+                _, ne, _, nh = tick(now, 0, 0, f"share {share}, cap 0")
+                assert (ne, nh) == (len(full_e), len(full_h))
+                # nothing was written, so every listed slot is still due; fewer than fit ...
+                ce, ch = {"n - 1": (max(ne - 1, 0), max(nh - 1, 0)), "1": (min(1, ne), min(1, nh)),
+                          "n // 2": (ne // 2, nh // 2)}[cut]
+                e1, ne1, h1, nh1 = tick(now, ce, ch, f"share {share}, cap {cut}")
+                assert (ne1, nh1, len(e1), len(h1)) == (ne, nh, ce, ch)
+                assert np.array_equal(e1, full_e[:ce]) and np.array_equal(h1, full_h[:ch])
+                # ... the slots past the cut are still due, the written ones are not ...
+                ed, hd = e.timers_store()
+                assert (ed[full_e[ce:]] <= now).all() and (ed[full_e[:ce]] > now).all(), (share, cut)
+                assert (hd[full_h[ch:]] <= now).all() and (hd[full_h[:ch]] > now).all(), (share, cut)
+                # ... and the second call returns exactly the remainder
+                e2, ne2, h2, nh2 = tick(now, gp, gp, f"share {share}, cap {cut}, remainder")
+                assert (ne2, nh2) == (ne - ce, nh - ch)
+                assert np.array_equal(e2, full_e[ce:]) and np.array_equal(h2, full_h[ch:])
+                assert tick(now, gp, gp, f"share {share}, cap {cut}, nothing left")[1::2] == (0, 0)
+                now += 3
             load_both(e, m, due_timers(rng, gp, now, share), due_timers(rng, gp, now, share))
             tick(now, gp + 5, gp + 5, f"share {share}, cap >= n")
             now += 3
@@ -278,12 +286,15 @@ def test_timers_note_all_kinds(P, seed):
 
 # ---- 4. mraft_clock_step on arbitrary states ------------------------------------------------
 
-def run_clock_case(P, G, send_all, where=HOST, shards=1):
+def run_clock_case(P, G, send_all, where=HOST, shards=1, mode=None):
     L, st, ed, hd, m = clock_case_model(P, G, send_all)
     with Engine(G, P, L) as e:
         e.load_state(st)
         if shards > 1:
             e.set_tick_shards(shards)
+        if mode is not None:
+            e.set_tick_mode(mode)
+            assert e.tick_mode() == mode
         e.timers_enable(CFG["seed"], CFG["heartbeat"], CFG["lo"], CFG["hi"], NOW0)
         e.timers_load(ed, hd)
         for k in range(CLOCK_STEPS):
@@ -319,6 +330,19 @@ def test_clock_step_two_tick_shards():
     assert stats["sender_stepped_down"] and stats["need_snapshot"]
 
 
+# 4b. Under the tick mode and the shard count the test sets. G = 33 with three
+# shards and G = 300 with two give uneven ranges and ranges shorter than a wave
+# of eight groups per segment; MRAFT_TICK_LIGHT feeds the light launch a
+# device-written leader_peer with many -1 entries, and its group_flags (or its
+# fallback's) feed step E.
+@pytest.mark.parametrize("where", [HOST, _abi.DEVICE], ids=["host", "device"])
+@pytest.mark.parametrize("shards", [1, 2, 3])
+@pytest.mark.parametrize("mode", [_abi.TICK_FULL, _abi.TICK_LIGHT, _abi.TICK_AUTO], ids=["full", "light", "auto"])
+@pytest.mark.parametrize("P,G,send_all", [(2, 33, False), (5, 300, True), (8, 300, False)])
+def test_clock_step_tick_modes_and_shards(P, G, send_all, mode, shards, where):
+    run_clock_case(P, G, send_all, where=where, shards=shards, mode=mode)
+
+
 def test_clock_step_optional_outputs():
     """Every output is optional: with none the step still does all its work."""
     P, G = 3, 300
@@ -345,16 +369,17 @@ class EngineNode:
         return self.e.clock_step(now, send_all)
 
 
-@pytest.mark.parametrize("G,P", SELF_SHAPES)
-def test_self_driving_run(G, P):
-    """From Make state the engine's history under clock steps alone — then a
-    crash and restart of every Leader, then Starts at the Leaders — is the
-    model's at every step (tests/test_timers_model.py checks what the model's
-    history must satisfy)."""
+def self_driving_case(G, P, shards=1, mode=None):
+    """Returns the light tick's fallback counts read after each leg-3 step."""
     L = SELF_L
     m = TimersModel(G, P, L)
+    fallbacks = []
     with Engine(G, P, L) as e:
         e.load_state(new_state(G, P, L))
+        if shards > 1:
+            e.set_tick_shards(shards)
+        if mode is not None:
+            e.set_tick_mode(mode)
         enable_both(e, m, dict(seed=SELF_CFG["seed"], heartbeat=SELF_CFG["heartbeat"], lo=SELF_CFG["lo"],
                                hi=SELF_CFG["hi"]))
 
@@ -362,8 +387,31 @@ def test_self_driving_run(G, P):
             for n in OUTS:
                 assert np.array_equal(outs[1][n], outs[0][n]), (t, n)
             same(e, m, f"tick {t}")
+            if t > 300 + 2 * SELF_CFG["hi"]:
+                fallbacks.append(e.tick_light_fallbacks())
 
         hist = self_driving([ModelNode(m), EngineNode(e)], G, P, check)
         assert len(hist) == 300 + 2 * SELF_CFG["hi"] + 40
         if P >= 2:
             assert (hist[max(hist)][0] == 1).all()
+    return fallbacks
+
+
+@pytest.mark.parametrize("G,P", SELF_SHAPES)
+def test_self_driving_run(G, P):
+    """From Make state the engine's history under clock steps alone — then a
+    crash and restart of every Leader, then Starts at the Leaders — is the
+    model's at every step (tests/test_timers_model.py checks what the model's
+    history must satisfy)."""
+    self_driving_case(G, P)
+
+
+@pytest.mark.parametrize("G,P", [(64, 5), (64, 2)])
+def test_self_driving_run_light_two_shards(G, P):
+    """The same run under MRAFT_TICK_LIGHT with two tick shards. With Leaders
+    in place and followers caught up the light launch settles groups itself:
+    after a leg-3 step fewer than G groups fell back to the full tick, so step
+    E consumed group_flags written by k_tick_lite, not only by its fallback."""
+    fallbacks = self_driving_case(G, P, shards=2, mode=_abi.TICK_LIGHT)
+    assert len(fallbacks) == 40 and min(fallbacks) >= 0, fallbacks
+    assert min(fallbacks) < G, fallbacks

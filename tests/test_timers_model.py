@@ -57,6 +57,30 @@ def test_draw_accepts_the_limits():
     assert 1 <= timer_draw(3, (1 << 31) - 1, 1 << 30, 1, 1 << 20, heartbeat=(1 << 30) - 1) < (1 << 20)
 
 
+def test_model_ticker_cut_lists_keep_the_rest_due():
+    """The buffer convention of mraft_ticker in the model: a listed slot that
+    does not fit keeps its due timer, and the next call returns exactly the
+    rest (the GPU tests compare the engine's cut lists with these)."""
+    G, P = 40, 3
+    gp = G * P
+    for cap in (0, 1, 7, gp):
+        m = TimersModel(G, P, 8)
+        m.o.st["state"][::4] = _abi.LEADER
+        m.enable(1, 9, 30, 60, 0)
+        m.load(np.where(np.arange(gp) % 3 == 0, 101, 100).astype(np.int32), np.full(gp, 100, np.int32))
+        leader = m.o.st["state"] == _abi.LEADER
+        full_e, full_h = np.nonzero((m.ed <= 100) & ~leader)[0], np.nonzero(leader)[0]
+        e1, ne, h1, nh = m.ticker(100, cap, cap)
+        assert (ne, nh) == (len(full_e), len(full_h))
+        assert np.array_equal(e1, full_e[:cap]) and np.array_equal(h1, full_h[:cap])
+        assert (m.ed[full_e[cap:]] <= 100).all() and (m.ed[full_e[:cap]] > 100).all()
+        assert (m.hd[full_h[cap:]] <= 100).all() and (m.hd[full_h[:cap]] > 100).all()
+        assert (m.hd[~leader] == 109).all()           # a non-leader's due heartbeat timer is reset, never listed
+        e2, ne2, h2, nh2 = m.ticker(100)
+        assert np.array_equal(e2, full_e[cap:]) and np.array_equal(h2, full_h[cap:])
+        assert m.ticker(100)[1::2] == (0, 0)
+
+
 # The first tick at which every group has exactly one Leader. With P = 2 the
 # last group is 25: its two replicas draw the same first deadline (46), both
 # stand at tick 46 and refuse each other, and their resets at 46 draw 39 and 41,

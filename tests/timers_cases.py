@@ -31,6 +31,19 @@ def due_timers(rng, n, now, share):
     return np.where(due, now - rng.integers(0, 3, n), now + rng.integers(1, 3, n)).astype(np.int32)
 
 
+def leaders_in_place_state(G, P, L, rng, seed):
+    """An election-storm state with a Leader sprinkled into 70 % of the groups
+    (P = 1: half of the replicas), as mraft_ticker's tests use it."""
+    from multiraft_amd._abi import LEADER
+    st, _ = synth_election_state(G, P, L, seed=seed, rounds=1)
+    if P > 1:
+        lead = rng.random(G) < 0.7
+        st["state"][np.nonzero(lead)[0] * P + rng.integers(0, P, int(lead.sum()))] = LEADER
+    else:
+        st["state"][rng.random(G * P) < 0.5] = LEADER
+    return st
+
+
 def clock_case(P, G, send_all):
     """(L, state, election_due, heartbeat_due) of one clock-step case. Even
     seeds take the tick fuzz generator's states (several Leaders per group at

@@ -261,6 +261,35 @@ class ModelNode:
 
     def __init__(self, model: TimersModel):
         self.m = model
+        self.G, self.P, self.L = model.G, model.P, model.L
+        # the message-level calls of the host-driven sequence (tests/timers_sequence.py)
+        o = model.o
+        self.start_election, self.handle_request_vote, self.process_vote_replies = (
+            o.start_election, o.handle_request_vote, o.process_vote_replies)
+        self.gather_append_args, self.handle_append_entries, self.process_append_replies = (
+            o.gather_append_args, o.handle_append_entries, o.process_append_replies)
+        self.election_rounds = o.election_rounds
+
+    def ticker(self, now, cap_e=None, cap_h=None):
+        return self.m.ticker(now, cap_e, cap_h)
+
+    def timers_enable(self, seed, heartbeat, election_lo, election_hi, now=0):
+        self.m.enable(seed, heartbeat, election_lo, election_hi, now)
+
+    def timers_note(self, kind, records, outcome, item_err, now):
+        self.m.note(kind, records, outcome, item_err, now)
+
+    def load_state(self, st):
+        self.m.o.load_state(st)
+
+    def store_state(self):
+        return self.m.o.store_state()
+
+    def timers_load(self, election_due=None, heartbeat_due=None):
+        self.m.load(election_due, heartbeat_due)
+
+    def timers_store(self):
+        return self.m.timers()
 
     def read_persistent(self, slots):
         return self.m.o.read_persistent(slots)
