@@ -14,7 +14,7 @@ from oracle_lib import Oracle, assert_states_equal  # noqa: E402
 
 from multiraft_amd import (Engine, entry_positions, synth_fold_batch, synth_seed, synth_tick_state,  # noqa: E402
                            )
-from multiraft_amd.engine import export_group_status_into  # noqa: E402
+from multiraft_amd.engine import export_group_status_into, new_state  # noqa: E402
 from multiraft_amd._abi import AE_ARGS, AE_RESULT, RV_ARGS, RV_RESULT  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -475,6 +475,85 @@ def test_applier_compact_snapshot_outputs_gpu():
         assert np.array_equal(si, osi[want]) and np.array_equal(stm, ost[want])
         assert not e.store_state()["has_snapshot"].any()
         assert_states_equal(e.store_state(), o.state(), G, P, L, "applier compact, snapshots")
+
+
+APPLY_BLOCK = 256    # slots per block of k_apply_count / k_apply_emit (their launch's blockDim)
+APPLY_CHUNK = 1024   # block counts per chunk of k_apply_scan (its part[1024])
+
+
+def _apply_scan_state(snaps):
+    """262,155 slots = 1,025 blocks of 256: block 1,024 is the one block of
+    k_apply_scan's second chunk, so its offsets are the running total carried
+    out of the first. commitIndex > lastApplied (and, with `snaps`,
+    hasSnapshot alone) set directly: the first and last slot of blocks 0,
+    1,023 and 1,024, one slot mid-block in each chunk, a sparse background."""
+    G, P, L = 52431, 5, 4
+    n = G * P
+    assert n == APPLY_CHUNK * APPLY_BLOCK + 11
+    st = new_state(G, P, L)
+    st["last_index"][:] = 3
+    st["log_term"][:] = 1
+    st["log_term"].reshape(n, L)[:, 0] = np.arange(n) % 5   # the dummy's term: SnapshotTerm
+    st["current_term"][:] = 1
+    B = APPLY_BLOCK
+    must = np.array([0, B - 1, 1023 * B, 1023 * B + B - 1, 1024 * B, n - 1, 500 * B + 77, 1024 * B + 5])
+    rng = np.random.default_rng(262155)
+    pend = rng.random(n) < 0.01
+    alone = np.array([1, B - 2, 1023 * B + 1, 1024 * B + 9])   # with `snaps`: hasSnapshot and no range
+    pend[1024 * B:] = False
+    pend[alone] = False
+    pend[must] = True
+    st["commit_index"][pend] = rng.integers(1, 4, int(pend.sum()))
+    st["last_applied"][pend] = st["commit_index"][pend] - rng.integers(1, 4, int(pend.sum()))
+    st["last_applied"] = np.maximum(st["last_applied"], 0)
+    if snaps:
+        hs = rng.random(n) < 0.005
+        hs[1024 * B:] = False
+        hs[must[::2]] = True                 # with a range behind the snapshot
+        hs[alone] = True
+        st["has_snapshot"][:] = hs
+    return G, P, L, st, must
+
+
+@pytest.mark.parametrize("variant", ["unlimited", "cap", "snapshots"])
+def test_applier_compact_second_scan_chunk_gpu(variant):
+    """The compacted applier where k_apply_scan runs a second chunk: count,
+    ascending slots and ranges against the dense oracle; with a cap that ends
+    inside block 1,024 only the listed slots advance, the second call returns
+    the remainder, a third nothing."""
+    snaps = variant == "snapshots"
+    G, P, L, st, must = _apply_scan_state(snaps)
+    o = Oracle(G, P, L, st)
+    with _engine(G, P, L, st) as e:
+        pre = e.store_state()
+        if snaps:
+            ofr, oto, osi, ost = o.collect_apply(snapshots=True)
+            want = np.nonzero((oto >= ofr) | (osi >= 0))[0]
+        else:
+            ofr, oto = o.collect_apply()
+            want = np.nonzero(oto >= ofr)[0]
+        assert set(must) <= set(want) and np.count_nonzero(want >= APPLY_CHUNK * APPLY_BLOCK) == 3 + snaps
+        cap = len(want) - 2 if variant == "cap" else None    # the last listed slot is block 1,024's first
+        out = e.collect_apply_compact(cap, snapshots=snaps)
+        sl, f, t, n = out[0], out[-3], out[-2], out[-1]
+        k = len(sl)
+        assert n == len(want) and k == (n if cap is None else cap)
+        assert np.array_equal(sl, want[:k]) and np.array_equal(f, ofr[want[:k]]) and np.array_equal(t, oto[want[:k]])
+        if snaps:
+            assert np.array_equal(out[1], osi[want]) and np.array_equal(out[2], ost[want])
+            assert np.count_nonzero((osi >= 0) & (oto < ofr)) >= 4
+        if cap is not None:
+            assert sl[-1] == APPLY_CHUNK * APPLY_BLOCK
+        got = e.store_state()
+        exp_applied = pre["last_applied"].copy()
+        adv = want[:k][pre["commit_index"][want[:k]] > pre["last_applied"][want[:k]]]
+        exp_applied[adv] = pre["commit_index"][adv]
+        assert np.array_equal(got["last_applied"], exp_applied)
+        out2 = e.collect_apply_compact(snapshots=snaps)
+        assert out2[-1] == n - k and np.array_equal(out2[0], want[k:])
+        assert np.array_equal(out2[-3], ofr[want[k:]]) and np.array_equal(out2[-2], oto[want[k:]])
+        assert e.collect_apply_compact(snapshots=snaps)[-1] == 0
+        assert_states_equal(e.store_state(), o.state(), G, P, L, f"applier compact, second scan chunk, {variant}")
 
 
 @pytest.mark.parametrize("S,G", [(2, 4096), (3, 4099), (8, 1031)])

@@ -306,6 +306,9 @@ def run_clock_case(P, G, send_all, where=HOST, shards=1, mode=None):
                 import torch
                 dev = {n: torch.zeros(G, dtype=torch.uint8 if n == "cand_mask" else torch.int32, device="cuda")
                        for n in OUTS}
+                # the fills run on torch's stream, the step on the engine's own non-blocking one: without
+                # this a fill can land after the step's store into the same buffer
+                torch.cuda.synchronize()
                 e.clock_step(NOW0 + k, send_all, where=_abi.DEVICE, out=dev)
                 e.synchronize()
                 got = {n: v.cpu().numpy() for n, v in dev.items()}
