@@ -44,12 +44,52 @@ constexpr int kDeferGridMax = 1 << 16;
 constexpr long long kLiteGridMin = 2048;
 constexpr long long kLiteGridUnknown = 8192;
 constexpr int kAutoProbe = 32;  // MRAFT_TICK_AUTO: a light tick at least every 32 ticks
-// The engine's pinned host words (device-written, read by the host when it
-// enqueues): [0] the last by-reference AppendEntries call's deferred count,
-// [1] the staged words of the last call that exceeded the stage (its need),
-// [kHintLite + s] the last light tick's fallback count of shard s.
-constexpr int kHintLite = 2;
-constexpr int kHintWords = kHintLite + kMaxShards;
+// The engine's pinned host words (device-written, read by the host through
+// hint() when it enqueues).
+enum Hint {
+  kHintDeferred,   // the last by-reference AppendEntries call's deferred count
+  kHintStageNeed,  // the staged words of the last call that exceeded the stage (its need)
+  kHintLite,       // + s: the last light tick's fallback count of shard s
+  kHintWords = kHintLite + kMaxShards
+};
+// The engine's grow-only device scratch buffers (scratch()), one slot per
+// purpose. A slot that several calls name (the folds' segment errors, the
+// persistence calls' headers and terms) is safe to share because calls on one
+// handle do not overlap, every call's work is ordered on the engine stream,
+// and each call writes a buffer before it reads it: nothing in these buffers
+// outlives the call that filled it. The one exception is kScrAeKin, whose
+// words carry the claim epoch of the call that wrote them and must survive
+// from call to call (ensure_claim zeroes it when the epoch wraps); no other
+// use may ever be given that slot. Stage (host-mode batches) maps a call's
+// k-th buffer to kScrStage0 + k, a range no other use reaches.
+constexpr int kStageMax = 7;  // buffers one call stages at most (mraft_start_and_tick)
+enum ScratchSlot {
+  kScrTickCount,     // mraft_replicate_tick_count: the counter stripes
+  kScrSegErr,        // the three reply folds: per-segment claim errors
+  kScrFoldScan,      // mraft_process_append_replies: launch_fold's scan lists
+  kScrPersistSlots,  // mraft_read_persistent: the slots
+  kScrPersistHdr,    // mraft_read_persistent, mraft_restore: the headers
+  kScrPersistTerms,  // mraft_read_persistent, mraft_restore: the terms
+  kScrRestoreErr,    // mraft_restore: the host's per-item verdicts
+  kScrApplyBlocks,   // mraft_collect_apply_compact: per-block counts
+  // AppendEntries by reference
+  kScrAeSoff,     // per item: its stage offset
+  kScrAeSetHead,  // per item: the set-head byte
+  kScrAeStage,    // the stage (mraft_set_stage_capacity)
+  kScrAeDefer,    // per stripe: the deferred items
+  kScrAeOrder,    // the ordered fallback's records and cycle buffers
+  kScrAeKin,      // the fallback's reader counts: epoch-tagged, persists across calls
+  // mraft_clock_step: the words one launch hands to the next when the caller
+  // gave no buffer for them, and the sender's terms
+  kScrClockLp,
+  kScrClockGf,
+  kScrClockCommit,
+  kScrClockTl,
+  kScrClockTg,
+  kScrTickerCnt,  // mraft_ticker: per-block counts of both lists
+  kScrStage0,     // Stage: kScrStage0 ... kScrStage0 + kStageMax - 1
+  kScrSlots = kScrStage0 + kStageMax
+};
 // MRAFT_STAGE_AUTO grows the stage to 5/4 of a batch's need, in 1 Mi-word
 // steps, up to 2^31 - 1 words (8 GiB).
 constexpr int64_t kStageStep = (int64_t)1 << 20;
@@ -81,8 +121,8 @@ struct mraft_engine {
   unsigned long long *ae_total = nullptr;  // AppendEntries by reference: the deferred launch's counters (mraft_kernels.hip)
   int64_t stage_cap = kDefaultStageWords;  // words of staged entries the deferred launch may use
   bool stage_auto = true;                  // MRAFT_STAGE_AUTO: grow stage_cap to the last overflow's need
-  long long *dhint = nullptr;  // pinned host word: the last by-reference call's deferred count (device-written)
-  long long *dhint_dev = nullptr;  // its device-side address
+  volatile long long *dhint = nullptr;  // the pinned host words (Hint): device-written
+  long long *dhint_dev = nullptr;       // their device-side address
   // the deferred launch's minimum grid: kDeferGridMin, or the environment's
   // MRAFT_DEFER_GRID_MIN at mraft_create (tests run the small-grid paths with it)
   long long defer_grid_min = kDeferGridMin;
@@ -99,8 +139,8 @@ struct mraft_engine {
   // configuration they were armed under
   int32_t *tm_ed = nullptr, *tm_hd = nullptr;
   mraft_timer_config tcfg{};
-  std::vector<void *> scratch_ptr;
-  std::vector<size_t> scratch_cap;
+  void *scratch_ptr[kScrSlots] = {};
+  size_t scratch_cap[kScrSlots] = {};
 };
 
 namespace {
@@ -177,14 +217,24 @@ int join_shards(mraft_engine *h) {
   return MRAFT_OK;
 }
 
-// Every entry point but the sharded tick: the handle is usable and earlier
-// sharded ticks are ordered before this call's work on the engine stream.
-int enter(mraft_engine *h) {
-  int rc = check(h);
-  if (rc) return rc;
+// The ticks' prologue: the handle is usable, on its device. The ticks do not
+// join earlier shard launches (launch_tick forks from the engine stream
+// instead): with tick shards, shard s's tick follows its own previous tick
+// only. A host-buffer tick joins them before its copies back.
+int enter_tick(mraft_engine *h) {
+  TRY(check(h));
   HIP_TRY(hipSetDevice(h->device));
+  return MRAFT_OK;
+}
+
+// Every other entry point's: also, earlier sharded ticks are ordered before
+// this call's work on the engine stream.
+int enter(mraft_engine *h) {
+  TRY(enter_tick(h));
   return join_shards(h);
 }
+
+long long hint(const mraft_engine *h, int k) { return h->dhint[k]; }
 
 // Host wait for everything the engine has enqueued (engine, shard and fan-in
 // streams). Errors are ignored (teardown paths).
@@ -250,35 +300,47 @@ mraft::Dev dev_slice(const mraft_engine *h, int32_t g0, int32_t g1) {
 
 int32_t *off(int32_t *p, int64_t k) { return p ? p + k : nullptr; }
 
-// The tick launch(es): one launch on the engine stream, or with S tick shards
-// one launch per contiguous group range on its own queue, each queue first
-// waiting for the engine stream's prior work (one event, fork_ev).
-int alloc_async(mraft_engine *h, void **p, size_t bytes, const char *what);
+// Device memory in stream order on the engine stream (hipMallocAsync /
+// hipFreeAsync): allocating or growing a buffer never waits for the device, so
+// MRAFT_DEVICE calls stay asynchronous when a batch is larger than any before
+// (include/mraft.h; VERDICT r5 item 2). A freed buffer is released after the
+// work already enqueued on the stream, which may still read it.
+int alloc_bytes(mraft_engine *h, void **p, size_t bytes, const char *what) {
+  *p = nullptr;
+  if (hipMallocAsync(p, bytes, h->stream) != hipSuccess || !*p) {
+    (void)hipGetLastError();
+    return fail(MRAFT_E_NOMEM, "%s: device allocation of %zu B failed", what, bytes);
+  }
+  return MRAFT_OK;
+}
+
+// alloc_bytes for n elements of T, zeroed or not (stream-ordered).
+template <class T>
+int alloc_async(mraft_engine *h, T **p, size_t n, const char *what, bool zero = false) {
+  void *v = nullptr;
+  const int rc = alloc_bytes(h, &v, sizeof(T) * n, what);
+  *p = (T *)v;
+  if (rc == MRAFT_OK && zero) HIP_TRY(hipMemsetAsync(v, 0, sizeof(T) * n, h->stream));
+  return rc;
+}
 
 // The light tick's buffers (MRAFT_TICK_LIGHT), allocated on first use,
 // stream-ordered, counters zeroed.
 int ensure_lite(mraft_engine *h) {
   if (h->lite_list) return MRAFT_OK;
-  void *l = nullptr, *c = nullptr;
   // a shard of G_s groups needs lite_list_words(G_s) <= G_s + 512 words
-  TRY(alloc_async(h, &l, ((size_t)h->G + 512 * kMaxShards) * sizeof(int32_t), "light tick list"));
-  h->lite_list = (int32_t *)l;
-  const size_t cb = (size_t)2 * kMaxShards * mraft::kLiteCntWords * sizeof(unsigned);
-  TRY(alloc_async(h, &c, cb, "light tick counters"));
-  h->lite_cnt = (unsigned *)c;
-  HIP_TRY(hipMemsetAsync(h->lite_cnt, 0, cb, h->stream));
+  TRY(alloc_async(h, &h->lite_list, (size_t)h->G + 512 * kMaxShards, "light tick list"));
+  TRY(alloc_async(h, &h->lite_cnt, (size_t)2 * kMaxShards * mraft::kLiteCntWords, "light tick counters", true));
   for (int s = 0; s < kMaxShards; ++s) h->lite_par[s] = 0;
   return MRAFT_OK;
 }
 
-// One tick launch over groups [g0, g0 + d.G) as shard s on stream st: the full
-// tick, or the light tick's pair of launches.
 // MRAFT_TICK_AUTO's choice for shard s of G_s groups: the light tick while
 // the last completed light tick sent at most a quarter of the groups to the
 // full tick (or none has completed yet); otherwise the full tick, with a
 // light tick every kAutoProbe-th tick to measure again.
 bool auto_light(mraft_engine *h, int s, int32_t gs) {
-  const long long last = ((volatile long long *)h->dhint)[kHintLite + s];
+  const long long last = hint(h, kHintLite + s);
   if (last < 0 || 4 * last <= (long long)gs) {
     h->auto_since[s] = 0;
     return true;
@@ -290,6 +352,8 @@ bool auto_light(mraft_engine *h, int s, int32_t gs) {
   return false;
 }
 
+// One tick launch over groups [g0, g0 + d.G) as shard s on stream st: the full
+// tick, or the light tick's pair of launches.
 // sio (mraft_start_and_tick): Start at the range's leaders first — inside the
 // light launch, or as its own launch before the full tick.
 void tick_range(mraft_engine *h, const mraft::Dev &d, int s, int32_t g0, const int32_t *lp, int32_t *gf,
@@ -310,7 +374,7 @@ void tick_range(mraft_engine *h, const mraft::Dev &d, int s, int32_t g0, const i
   lb.cnt = h->lite_cnt + (2 * s + par) * mraft::kLiteCntWords;
   lb.cnt_next = h->lite_cnt + (2 * s + (par ^ 1)) * mraft::kLiteCntWords;
   lb.hint = h->dhint_dev + kHintLite + s;
-  const long long prev = ((volatile long long *)h->dhint)[kHintLite + s];
+  const long long prev = hint(h, kHintLite + s);
   // no completed light tick yet (e.g. the first ticks enqueued back to back):
   // one wave per SIMD slot, grid-stride
   const long long gr = prev < 0 ? kLiteGridUnknown : std::max(kLiteGridMin, 2 * prev);
@@ -318,6 +382,9 @@ void tick_range(mraft_engine *h, const mraft::Dev &d, int s, int32_t g0, const i
   mraft::launch_replicate_tick_light(d, lp + g0, off(gf, g0), off(ec, g0), off(et, g0), lb, sio ? &so : nullptr, st);
 }
 
+// The tick launch(es): one launch on the engine stream, or with S tick shards
+// one launch per contiguous group range on its own queue, each queue first
+// waiting for the engine stream's prior work (one event, fork_ev).
 int launch_tick(mraft_engine *h, const int32_t *lp, int32_t *gf, int32_t *ec, int32_t *et,
                 const mraft::StartIO *sio = nullptr) {
   if (h->tick_mode != MRAFT_TICK_FULL) TRY(ensure_lite(h));
@@ -338,102 +405,167 @@ int launch_tick(mraft_engine *h, const int32_t *lp, int32_t *gf, int32_t *ec, in
   return MRAFT_OK;
 }
 
-// Device memory in stream order on the engine stream (hipMallocAsync /
-// hipFreeAsync): allocating or growing a buffer never waits for the device, so
-// MRAFT_DEVICE calls stay asynchronous when a batch is larger than any before
-// (include/mraft.h; VERDICT r5 item 2). A freed buffer is released after the
-// work already enqueued on the stream, which may still read it.
-int alloc_async(mraft_engine *h, void **p, size_t bytes, const char *what) {
-  *p = nullptr;
-  if (hipMallocAsync(p, bytes, h->stream) != hipSuccess || !*p) {
-    (void)hipGetLastError();
-    return fail(MRAFT_E_NOMEM, "%s: device allocation of %zu B failed", what, bytes);
+// Grow-only device scratch slot of at least `bytes` (stream-ordered: no host
+// wait); *grew (optional) tells whether the buffer is a new one.
+int scratch_bytes(mraft_engine *h, ScratchSlot slot, size_t bytes, void **out, bool *grew = nullptr) {
+  if (bytes == 0) bytes = 16;
+  const bool grows = h->scratch_cap[slot] < bytes;
+  if (grows) {
+    if (h->scratch_ptr[slot]) HIP_TRY(hipFreeAsync(h->scratch_ptr[slot], h->stream));
+    h->scratch_cap[slot] = 0;
+    TRY(alloc_bytes(h, &h->scratch_ptr[slot], bytes, "scratch"));
+    h->scratch_cap[slot] = bytes;
   }
+  if (grew) *grew = grows;
+  *out = h->scratch_ptr[slot];
   return MRAFT_OK;
 }
 
-// Grow-only device scratch slot `idx` (stream-ordered: no host wait).
-int scratch(mraft_engine *h, size_t idx, size_t bytes, void **out) {
-  if (h->scratch_ptr.size() <= idx) {
-    h->scratch_ptr.resize(idx + 1, nullptr);
-    h->scratch_cap.resize(idx + 1, 0);
-  }
-  if (bytes == 0) bytes = 16;
-  if (h->scratch_cap[idx] < bytes) {
-    if (h->scratch_ptr[idx]) HIP_TRY(hipFreeAsync(h->scratch_ptr[idx], h->stream));
-    h->scratch_ptr[idx] = nullptr;
-    h->scratch_cap[idx] = 0;
-    void *p = nullptr;
-    TRY(alloc_async(h, &p, bytes, "scratch"));
-    h->scratch_ptr[idx] = p;
-    h->scratch_cap[idx] = bytes;
-  }
-  *out = h->scratch_ptr[idx];
-  return MRAFT_OK;
+// scratch_bytes for n elements of T.
+template <class T>
+int scratch(mraft_engine *h, ScratchSlot slot, size_t n, T **out) {
+  void *p = nullptr;
+  const int rc = scratch_bytes(h, slot, sizeof(T) * n, &p);
+  *out = (T *)p;
+  return rc;
 }
 
 // scratch() whose new buffer is zeroed when it is (re)allocated (stream-ordered):
 // for epoch-tagged counters, whose stale contents must never carry a tag a
 // later call could take for its own.
-int scratch_zeroed(mraft_engine *h, size_t idx, size_t bytes, void **out) {
-  const bool grows = h->scratch_ptr.size() <= idx || h->scratch_cap[idx] < (bytes ? bytes : 16);
-  TRY(scratch(h, idx, bytes, out));
-  if (grows) HIP_TRY(hipMemsetAsync(*out, 0, h->scratch_cap[idx], h->stream));
+template <class T>
+int scratch_zeroed(mraft_engine *h, ScratchSlot slot, size_t n, T **out) {
+  void *p = nullptr;
+  bool grew = false;
+  TRY(scratch_bytes(h, slot, sizeof(T) * n, &p, &grew));
+  if (grew) HIP_TRY(hipMemsetAsync(p, 0, h->scratch_cap[slot], h->stream));
+  *out = (T *)p;
   return MRAFT_OK;
 }
 
 // Batch pointer staging: for MRAFT_HOST, input buffers are copied to device
-// scratch and output buffers are copied back by finish().
+// scratch (the call's k-th buffer to slot kScrStage0 + k) and output buffers
+// are copied back by finish(); for MRAFT_DEVICE the caller's pointer is used
+// as it is. A null pointer maps to null. The first failure sticks: the maps
+// after it do nothing, and status() reports it before anything is launched.
 struct Stage {
   mraft_engine *h;
   bool host;
-  size_t next_slot = 0;
-  struct Out { void *host; void *dev; size_t bytes; };
-  std::vector<Out> outs;
+  int rc = MRAFT_OK, n_map = 0, n_out = 0;
+  struct Out { void *host; void *dev; size_t bytes; } outs[kStageMax];
   Stage(mraft_engine *hh, int32_t where) : h(hh), host(where == MRAFT_HOST) {}
 
-  // in: read by the kernel; out: written by the kernel; both: read and written.
-  int map(const void *p, size_t bytes, bool in, bool out, void **dptr) {
-    if (!p) { *dptr = nullptr; return MRAFT_OK; }
-    if (!host) { *dptr = const_cast<void *>(p); return MRAFT_OK; }
-    void *d = nullptr;
-    int rc = scratch(h, 8 + next_slot++, bytes, &d);
-    if (rc) return rc;
-    if (in && bytes) HIP_TRY(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, h->stream));
-    if (out) outs.push_back({const_cast<void *>(p), d, bytes});
-    *dptr = d;
-    return MRAFT_OK;
-  }
+  // in: n elements read by the kernel; out: n elements written by it.
+  template <class T>
+  const T *in(const T *p, size_t n) { return (const T *)map(p, sizeof(T) * n, true); }
+  template <class T>
+  T *out(T *p, size_t n) { return (T *)map(p, sizeof(T) * n, false); }
+  int status() const { return rc; }
   int finish() {
     HIP_TRY(hipGetLastError());
     if (!host) return MRAFT_OK;
-    for (auto &o : outs)
-      if (o.bytes) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, h->stream));
+    for (int k = 0; k < n_out; ++k)
+      if (outs[k].bytes)
+        HIP_TRY(hipMemcpyAsync(outs[k].host, outs[k].dev, outs[k].bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return MRAFT_OK;
+  }
+
+ private:
+  void *map(const void *p, size_t bytes, bool in) {
+    if (!p || rc) return nullptr;
+    if (!host) return const_cast<void *>(p);
+    void *d = nullptr;
+    rc = n_map == kStageMax ? fail(MRAFT_E_INVAL, "internal: a call stages more than %d buffers", kStageMax)
+                            : scratch_bytes(h, (ScratchSlot)(kScrStage0 + n_map++), bytes, &d);
+    if (rc == MRAFT_OK && in && bytes) rc = copy(d, p, bytes);
+    if (rc) return nullptr;
+    if (!in) outs[n_out++] = {const_cast<void *>(p), d, bytes};
+    return d;
+  }
+  int copy(void *d, const void *p, size_t bytes) {
+    HIP_TRY(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, h->stream));
     return MRAFT_OK;
   }
 };
 
-
+// The claim words (and the by-reference handler's source marks), allocated on
+// first use, and the next claim epoch. Only for calls with n > 0: an empty
+// call does not advance the epoch.
 int ensure_claim(mraft_engine *h) {
+  const size_t gp = (size_t)gp_of(h);
   if (!h->claim) {
-    size_t b = (size_t)gp_of(h) * sizeof(unsigned long long);
-    void *c = nullptr, *m = nullptr;
-    TRY(alloc_async(h, &c, b, "claim"));
-    h->claim = (unsigned long long *)c;
-    HIP_TRY(hipMemsetAsync(h->claim, 0, b, h->stream));
-    TRY(alloc_async(h, &m, (size_t)gp_of(h) * sizeof(uint32_t), "srcmark"));
-    h->srcmark = (uint32_t *)m;
-    HIP_TRY(hipMemsetAsync(h->srcmark, 0, (size_t)gp_of(h) * sizeof(uint32_t), h->stream));
+    TRY(alloc_async(h, &h->claim, gp, "claim", true));
+    TRY(alloc_async(h, &h->srcmark, gp, "srcmark", true));
   }
   if (++h->epoch == 0) {  // wrapped: reset (and every epoch-tagged counter)
-    HIP_TRY(hipMemsetAsync(h->claim, 0, (size_t)gp_of(h) * sizeof(unsigned long long), h->stream));
-    HIP_TRY(hipMemsetAsync(h->srcmark, 0, (size_t)gp_of(h) * sizeof(uint32_t), h->stream));
-    if (h->scratch_ptr.size() > 20 && h->scratch_ptr[20])
-      HIP_TRY(hipMemsetAsync(h->scratch_ptr[20], 0, h->scratch_cap[20], h->stream));
+    HIP_TRY(hipMemsetAsync(h->claim, 0, gp * sizeof *h->claim, h->stream));
+    HIP_TRY(hipMemsetAsync(h->srcmark, 0, gp * sizeof *h->srcmark, h->stream));
+    if (h->scratch_ptr[kScrAeKin])
+      HIP_TRY(hipMemsetAsync(h->scratch_ptr[kScrAeKin], 0, h->scratch_cap[kScrAeKin], h->stream));
     h->epoch = 1;
   }
   return MRAFT_OK;
+}
+
+// The duplicate-slot claims of a batch of records (their slot member) or of
+// bare slots, per item or per segment: stride and offset follow from the type.
+template <class Rec>
+constexpr int slot_offset() { return offsetof(Rec, slot); }
+template <>
+constexpr int slot_offset<int32_t>() { return 0; }
+template <class Rec>
+void claim(mraft_engine *h, const Rec *items, int64_t n, const int64_t *seg_begin, int32_t *err) {
+  mraft::launch_claim(items, n, sizeof(Rec), slot_offset<Rec>(), seg_begin, gp_of(h), h->P, h->claim, h->epoch, err,
+                      h->stream);
+}
+
+// What the three reply folds share (mraft_process_*_replies): the argument
+// checks, the next claim epoch, the staged buffers and the per-segment claim
+// errors; launch(b) then enqueues the fold's own work.
+template <class Rec>
+struct FoldBufs {
+  const Rec *it;
+  const int64_t *sb;
+  int64_t ns;
+  int32_t *se, *fl, *e;
+};
+template <class Rec, class Launch>
+int fold_replies(mraft_engine *h, const Rec *items, int64_t n, const int64_t *seg_begin, int64_t n_seg,
+                 int32_t *out_flags, int32_t *item_err, int32_t where, Launch launch) {
+  TRY(enter(h));
+  if (n < 0 || (n > 0 && (!items || !out_flags || !item_err)))
+    return fail(MRAFT_E_INVAL, "null argument");
+  if (seg_begin && n_seg < 0) return fail(MRAFT_E_INVAL, "n_seg < 0");
+  if (n == 0) return MRAFT_OK;
+  TRY(ensure_claim(h));
+  Stage sg(h, where);
+  FoldBufs<Rec> b{};
+  b.it = sg.in(items, n);
+  b.sb = sg.in(seg_begin, seg_begin ? n_seg + 1 : 0);
+  b.ns = seg_begin ? n_seg : n;
+  b.fl = sg.out(out_flags, n);
+  b.e = sg.out(item_err, n);
+  TRY(sg.status());
+  TRY(scratch(h, kScrSegErr, (size_t)b.ns, &b.se));
+  TRY(launch(b));
+  return sg.finish();
+}
+
+// The InstallSnapshot and RequestVote folds: the outputs zeroed, the segment
+// claims, then `fold` (launch_process_is, launch_tally).
+template <class Rec>
+int fold_records(mraft_engine *h, const Rec *items, int64_t n, const int64_t *seg_begin, int64_t n_seg,
+                 int32_t *out_flags, int32_t *item_err, int32_t where,
+                 void (*fold)(const mraft::Dev &, const Rec *, int64_t, const int64_t *, int64_t, int32_t *, int32_t *,
+                              int32_t *, hipStream_t)) {
+  return fold_replies(h, items, n, seg_begin, n_seg, out_flags, item_err, where, [=](const FoldBufs<Rec> &b) -> int {
+    HIP_TRY(hipMemsetAsync(b.fl, 0, sizeof(int32_t) * n, h->stream));
+    HIP_TRY(hipMemsetAsync(b.e, 0, sizeof(int32_t) * n, h->stream));
+    claim(h, b.it, b.ns, b.sb, b.se);
+    fold(dev_of(h), b.it, n, b.sb, b.ns, b.se, b.fl, b.e, h->stream);
+    return MRAFT_OK;
+  });
 }
 
 void free_owned(mraft_engine *h) {
@@ -445,6 +577,82 @@ void free_owned(mraft_engine *h) {
   }
   h->owned = false;
   h->bound = false;
+}
+
+// The stream, the pinned words and (without MRAFT_CREATE_NO_ALLOC) the state
+// arrays of a new handle. On failure the handle is left partly built, for
+// teardown().
+int create_parts(mraft_engine *h, uint32_t flags) {
+  if (flags & MRAFT_CREATE_DEDICATED_QUEUE)
+    TRY(make_queue(h, true, &h->own_stream));
+  else if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess)
+    return fail(MRAFT_E_HIP, "hipStreamCreate failed");
+  h->stream = h->own_stream;
+  void *hp = nullptr, *dp = nullptr;
+  if (hipHostMalloc(&hp, sizeof(long long) * kHintWords, hipHostMallocMapped) != hipSuccess)
+    return fail(MRAFT_E_NOMEM, "pinned host word allocation failed");
+  h->dhint = (volatile long long *)hp;
+  h->dhint[kHintDeferred] = 0;
+  h->dhint[kHintStageNeed] = 0;
+  for (int s = 0; s < kMaxShards; ++s) h->dhint[kHintLite + s] = -1;  // no light tick yet
+  if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) return fail(MRAFT_E_HIP, "hipHostGetDevicePointer failed");
+  h->dhint_dev = (long long *)dp;
+  if (flags & MRAFT_CREATE_NO_ALLOC) return MRAFT_OK;
+  h->owned = true;
+  for (const auto &a : kArrays)
+    if (hipMalloc(&(h->dev.*(a.ptr)), arr_bytes(h, a.kind)) != hipSuccess)
+      return fail(MRAFT_E_NOMEM, "device state allocation failed (G=%d P=%d L=%d)", h->G, h->P, h->L);
+  h->bound = true;
+  (void)hipMemsetAsync(h->dev.log_term, 0, arr_bytes(h, 1), h->stream);
+  (void)hipMemsetAsync(h->dev.match_index, 0, arr_bytes(h, 2), h->stream);
+  (void)hipMemsetAsync(h->dev.next_index, 0, arr_bytes(h, 2), h->stream);
+  mraft::launch_init_state(dev_of(h), h->stream);
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(MRAFT_E_HIP, "init failed: %s", hipGetErrorString(e));
+  return MRAFT_OK;
+}
+
+// Waits for the handle's work and releases everything it owns, then the
+// handle. Every member is null until it is made, so a partly built handle
+// (a failed mraft_create) takes the same path; one without a stream has
+// enqueued nothing.
+void teardown(mraft_engine *h) {
+  (void)hipSetDevice(h->device);
+  if (h->stream) drain(h);
+  free_owned(h);
+  if (h->stream) {
+    // stream-ordered buffers (alloc_async): freed on the engine stream, then waited for
+    for (void *p : h->scratch_ptr)
+      if (p) (void)hipFreeAsync(p, h->stream);
+    for (void *p : {(void *)h->claim, (void *)h->srcmark, (void *)h->ae_total, (void *)h->lite_list,
+                    (void *)h->lite_cnt, (void *)h->tm_ed, (void *)h->tm_hd})
+      if (p) (void)hipFreeAsync(p, h->stream);
+    (void)hipStreamSynchronize(h->stream);
+  }
+  if (h->fanin_own) (void)hipStreamSynchronize(h->fanin_own);
+  if (h->fanin_masked) (void)hipStreamSynchronize(h->fanin_masked);
+  destroy_shard_queues(h);
+  for (hipStream_t s : {h->own_stream, h->fanin_own, h->fanin_masked, h->tick_masked})
+    if (s) (void)hipStreamDestroy(s);
+  if (h->fanin_ev) (void)hipEventDestroy(h->fanin_ev);
+  if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
+  if (h->dhint) (void)hipHostFree((void *)h->dhint);
+  delete h;
+}
+
+// One array of a load (into the engine's `eng`) or a store (out of it): the
+// caller's array `usr` is host or device memory (`where`), and a null one is
+// skipped. finish_copies() ends the call: a host-mode one waits for its copies.
+int copy_array(mraft_engine *h, bool load, int32_t *eng, int32_t *usr, size_t bytes, int32_t where) {
+  if (!usr) return MRAFT_OK;
+  const hipMemcpyKind k = where != MRAFT_HOST ? hipMemcpyDeviceToDevice : load ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  HIP_TRY(hipMemcpyAsync(load ? eng : usr, load ? usr : eng, bytes, k, h->stream));
+  return MRAFT_OK;
+}
+
+int finish_copies(mraft_engine *h, int32_t where) {
+  if (where == MRAFT_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
+  return MRAFT_OK;
 }
 
 }  // namespace
@@ -470,90 +678,17 @@ int mraft_create(int32_t groups, int32_t peers, int32_t log_capacity, int32_t de
     const long long v = atoll(e);
     if (v >= 1 && v <= kDeferGridMax) h->defer_grid_min = v;
   }
-  if (flags & MRAFT_CREATE_DEDICATED_QUEUE) {
-    const int rc = make_queue(h, true, &h->own_stream);
-    if (rc) {
-      delete h;
-      return rc;
-    }
-  } else if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
-    return fail(MRAFT_E_HIP, "hipStreamCreate failed");
-  }
-  h->stream = h->own_stream;
-  {
-    void *hp = nullptr;
-    if (hipHostMalloc(&hp, sizeof(long long) * kHintWords, hipHostMallocMapped) != hipSuccess) {
-      (void)hipStreamDestroy(h->own_stream);
-      delete h;
-      return fail(MRAFT_E_NOMEM, "pinned host word allocation failed");
-    }
-    h->dhint = (long long *)hp;
-    *(volatile long long *)h->dhint = 0;
-    ((volatile long long *)h->dhint)[1] = 0;
-    for (int k = 0; k < kMaxShards; ++k) ((volatile long long *)h->dhint)[kHintLite + k] = -1;  // no light tick yet
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
-      (void)hipHostFree(hp);
-      (void)hipStreamDestroy(h->own_stream);
-      delete h;
-      return fail(MRAFT_E_HIP, "hipHostGetDevicePointer failed");
-    }
-    h->dhint_dev = (long long *)dp;
-  }
-  if (!(flags & MRAFT_CREATE_NO_ALLOC)) {
-    h->owned = true;
-    for (const auto &a : kArrays) {
-      int32_t *p = nullptr;
-      if (hipMalloc(&p, arr_bytes(h, a.kind)) != hipSuccess) {
-        free_owned(h);
-        (void)hipStreamDestroy(h->own_stream);
-        (void)hipHostFree(h->dhint);
-        delete h;
-        return fail(MRAFT_E_NOMEM, "device state allocation failed (G=%d P=%d L=%d)", groups, peers,
-                    log_capacity);
-      }
-      h->dev.*(a.ptr) = p;
-    }
-    h->bound = true;
-    (void)hipMemsetAsync(h->dev.log_term, 0, arr_bytes(h, 1), h->stream);
-    (void)hipMemsetAsync(h->dev.match_index, 0, arr_bytes(h, 2), h->stream);
-    (void)hipMemsetAsync(h->dev.next_index, 0, arr_bytes(h, 2), h->stream);
-    mraft::launch_init_state(dev_of(h), h->stream);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-      free_owned(h);
-      (void)hipStreamDestroy(h->own_stream);
-      (void)hipHostFree(h->dhint);
-      delete h;
-      return fail(MRAFT_E_HIP, "init failed: %s", hipGetErrorString(e));
-    }
+  const int rc = create_parts(h, flags);
+  if (rc) {
+    teardown(h);
+    return rc;
   }
   *out = h;
   return MRAFT_OK;
 }
 
 int mraft_destroy(mraft_engine *h) {
-  if (!h) return MRAFT_OK;
-  (void)hipSetDevice(h->device);
-  drain(h);
-  free_owned(h);
-  // stream-ordered buffers (alloc_async): freed on the engine stream, then waited for
-  for (void *p : h->scratch_ptr)
-    if (p) (void)hipFreeAsync(p, h->stream);
-  for (void *p : {(void *)h->claim, (void *)h->srcmark, (void *)h->ae_total, (void *)h->lite_list, (void *)h->lite_cnt,
-                  (void *)h->tm_ed, (void *)h->tm_hd})
-    if (p) (void)hipFreeAsync(p, h->stream);
-  (void)hipStreamSynchronize(h->stream);
-  if (h->fanin_own) (void)hipStreamSynchronize(h->fanin_own);
-  if (h->fanin_masked) (void)hipStreamSynchronize(h->fanin_masked);
-  destroy_shard_queues(h);
-  for (hipStream_t s : {h->own_stream, h->fanin_own, h->fanin_masked, h->tick_masked})
-    if (s) (void)hipStreamDestroy(s);
-  if (h->fanin_ev) (void)hipEventDestroy(h->fanin_ev);
-  if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
-  if (h->dhint) (void)hipHostFree(h->dhint);
-  delete h;
+  if (h) teardown(h);
   return MRAFT_OK;
 }
 
@@ -615,28 +750,19 @@ int mraft_dims(const mraft_engine *h, int32_t *g, int32_t *p, int32_t *l) {
 int mraft_load_state(mraft_engine *h, const mraft_soa *src, int32_t where) {
   TRY(enter(h));
   if (!src) return fail(MRAFT_E_INVAL, "src is null");
-  HIP_TRY(hipSetDevice(h->device));
-  const hipMemcpyKind k = where == MRAFT_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   for (const auto &a : kArrays)
     if (!(src->*(a.ptr))) return fail(MRAFT_E_INVAL, "load_state: every array is required");
-  for (const auto &a : kArrays)
-    HIP_TRY(hipMemcpyAsync(h->dev.*(a.ptr), src->*(a.ptr), arr_bytes(h, a.kind), k, h->stream));
+  for (const auto &a : kArrays) TRY(copy_array(h, true, h->dev.*(a.ptr), src->*(a.ptr), arr_bytes(h, a.kind), where));
   mraft::launch_terms_sorted(dev_of(h), h->stream);  // the engine's own proof, not the source's claim
   HIP_TRY(hipGetLastError());
-  if (where == MRAFT_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
-  return MRAFT_OK;
+  return finish_copies(h, where);
 }
 
 int mraft_store_state(mraft_engine *h, const mraft_soa *dst, int32_t where) {
   TRY(enter(h));
   if (!dst) return fail(MRAFT_E_INVAL, "dst is null");
-  HIP_TRY(hipSetDevice(h->device));
-  const hipMemcpyKind k = where == MRAFT_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  for (const auto &a : kArrays)
-    if (dst->*(a.ptr))
-      HIP_TRY(hipMemcpyAsync(dst->*(a.ptr), h->dev.*(a.ptr), arr_bytes(h, a.kind), k, h->stream));
-  if (where == MRAFT_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
-  return MRAFT_OK;
+  for (const auto &a : kArrays) TRY(copy_array(h, false, h->dev.*(a.ptr), dst->*(a.ptr), arr_bytes(h, a.kind), where));
+  return finish_copies(h, where);
 }
 
 int mraft_state_view(mraft_engine *h, mraft_soa *out) {
@@ -662,19 +788,15 @@ int mraft_bind_state(mraft_engine *h, const mraft_soa *d) {
 
 // ---------------------------------------------------------------- hot path
 
-// The ticks do not join earlier shard launches (launch_tick forks from the
-// engine stream instead): with tick shards, shard s's tick follows its own
-// previous tick only. A host-buffer tick joins them before its copies back.
 int mraft_replicate_tick(mraft_engine *h, const int32_t *leader_peer, int32_t *group_flags,
                          int32_t where) {
-  TRY(check(h));
+  TRY(enter_tick(h));
   if (!leader_peer) return fail(MRAFT_E_INVAL, "leader_peer is null");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *lp, *gf;
-  TRY(sg.map(leader_peer, sizeof(int32_t) * h->G, true, false, &lp));
-  TRY(sg.map(group_flags, sizeof(int32_t) * h->G, false, true, &gf));
-  TRY(launch_tick(h, (const int32_t *)lp, (int32_t *)gf, nullptr, nullptr));
+  const int32_t *lp = sg.in(leader_peer, h->G);
+  int32_t *gf = sg.out(group_flags, h->G);
+  TRY(sg.status());
+  TRY(launch_tick(h, lp, gf, nullptr, nullptr));
   if (where == MRAFT_HOST) TRY(join_shards(h));
   return sg.finish();
 }
@@ -682,38 +804,30 @@ int mraft_replicate_tick(mraft_engine *h, const int32_t *leader_peer, int32_t *g
 int mraft_start_and_tick(mraft_engine *h, const int32_t *leader_peer, const int32_t *counts, int32_t *out_index,
                          int32_t *out_term, int32_t *out_is_leader, int32_t *item_err, int32_t *group_flags,
                          int32_t where) {
-  TRY(check(h));
+  TRY(enter_tick(h));
   if (!leader_peer || !counts || !out_index || !out_term || !out_is_leader || !item_err)
     return fail(MRAFT_E_INVAL, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *lp, *c, *oi, *ot, *ol, *e, *gf;
-  const size_t gb = sizeof(int32_t) * h->G;
-  TRY(sg.map(leader_peer, gb, true, false, &lp));
-  TRY(sg.map(counts, gb, true, false, &c));
-  TRY(sg.map(out_index, gb, false, true, &oi));
-  TRY(sg.map(out_term, gb, false, true, &ot));
-  TRY(sg.map(out_is_leader, gb, false, true, &ol));
-  TRY(sg.map(item_err, gb, false, true, &e));
-  TRY(sg.map(group_flags, gb, false, true, &gf));
-  const mraft::StartIO sio{(const int32_t *)c, (int32_t *)oi, (int32_t *)ot, (int32_t *)ol, (int32_t *)e};
-  TRY(launch_tick(h, (const int32_t *)lp, (int32_t *)gf, nullptr, nullptr, &sio));
+  const size_t G = h->G;
+  const int32_t *lp = sg.in(leader_peer, G);
+  const mraft::StartIO sio{sg.in(counts, G), sg.out(out_index, G), sg.out(out_term, G), sg.out(out_is_leader, G),
+                           sg.out(item_err, G)};
+  int32_t *gf = sg.out(group_flags, G);
+  TRY(sg.status());
+  TRY(launch_tick(h, lp, gf, nullptr, nullptr, &sio));
   if (where == MRAFT_HOST) TRY(join_shards(h));
   return sg.finish();
 }
 
 int mraft_replicate_tick_export(mraft_engine *h, const int32_t *leader_peer, int32_t *group_flags,
                                 int32_t *commit, int32_t *term_leader, int32_t where) {
-  TRY(check(h));
+  TRY(enter_tick(h));
   if (!leader_peer || !commit || !term_leader) return fail(MRAFT_E_INVAL, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *lp, *gf, *c, *t;
-  TRY(sg.map(leader_peer, sizeof(int32_t) * h->G, true, false, &lp));
-  TRY(sg.map(group_flags, sizeof(int32_t) * h->G, false, true, &gf));
-  TRY(sg.map(commit, sizeof(int32_t) * h->G, false, true, &c));
-  TRY(sg.map(term_leader, sizeof(int32_t) * h->G, false, true, &t));
-  TRY(launch_tick(h, (const int32_t *)lp, (int32_t *)gf, (int32_t *)c, (int32_t *)t));
+  const int32_t *lp = sg.in(leader_peer, h->G);
+  int32_t *gf = sg.out(group_flags, h->G), *c = sg.out(commit, h->G), *t = sg.out(term_leader, h->G);
+  TRY(sg.status());
+  TRY(launch_tick(h, lp, gf, c, t));
   if (where == MRAFT_HOST) TRY(join_shards(h));
   return sg.finish();
 }
@@ -722,18 +836,17 @@ int mraft_replicate_tick_count(mraft_engine *h, const int32_t *leader_peer, int6
                                int32_t where) {
   TRY(enter(h));
   if (!leader_peer || !out_words) return fail(MRAFT_E_INVAL, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *lp, *cnt;
-  TRY(sg.map(leader_peer, sizeof(int32_t) * h->G, true, false, &lp));
+  const int32_t *lp = sg.in(leader_peer, h->G);
+  TRY(sg.status());
   constexpr size_t cw = (size_t)mraft::kCountStripes * mraft::kCountWords;
-  TRY(scratch(h, 0, cw * sizeof(unsigned long long), &cnt));
-  HIP_TRY(hipMemsetAsync(cnt, 0, cw * sizeof(unsigned long long), h->stream));
-  mraft::launch_replicate_tick_count(dev_of(h), (const int32_t *)lp, (unsigned long long *)cnt,
-                                     h->stream);
+  unsigned long long *cnt;
+  TRY(scratch(h, kScrTickCount, cw, &cnt));
+  HIP_TRY(hipMemsetAsync(cnt, 0, cw * sizeof *cnt, h->stream));
+  mraft::launch_replicate_tick_count(dev_of(h), lp, cnt, h->stream);
   HIP_TRY(hipGetLastError());
-  std::vector<unsigned long long> hc(cw);
-  HIP_TRY(hipMemcpyAsync(hc.data(), cnt, cw * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  unsigned long long hc[cw];
+  HIP_TRY(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (int i = 0; i < 3; ++i) {
     unsigned long long t = 0;
@@ -749,15 +862,12 @@ int mraft_gather_append_args(mraft_engine *h, const int32_t *slots, const int32_
   if (n < 0 || (n > 0 && (!slots || !peers || !out_args || !item_err)))
     return fail(MRAFT_E_INVAL, "null argument");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *s, *p, *o, *e;
-  TRY(sg.map(slots, sizeof(int32_t) * n, true, false, &s));
-  TRY(sg.map(peers, sizeof(int32_t) * n, true, false, &p));
-  TRY(sg.map(out_args, sizeof(mraft_ae_args) * n, false, true, &o));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  mraft::launch_gather_args(dev_of(h), (const int32_t *)s, (const int32_t *)p, n,
-                            (mraft_ae_args *)o, (int32_t *)e, h->stream);
+  const int32_t *s = sg.in(slots, n), *p = sg.in(peers, n);
+  mraft_ae_args *o = sg.out(out_args, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
+  mraft::launch_gather_args(dev_of(h), s, p, n, o, e, h->stream);
   return sg.finish();
 }
 
@@ -778,79 +888,67 @@ int mraft_handle_append_entries_ex(mraft_engine *h, const mraft_ae_args *args, i
   if (n > INT32_MAX) return fail(MRAFT_E_INVAL, "n = %lld items exceeds 2^31 - 1", (long long)n);
   if (entry_terms && n_entry_terms < 0) return fail(MRAFT_E_INVAL, "n_entry_terms < 0");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   TRY(ensure_claim(h));
   Stage sg(h, where);
-  void *a, *en, *r, *e, *rs;
-  TRY(sg.map(args, sizeof(mraft_ae_args) * n, true, false, &a));
-  TRY(sg.map(entry_terms, sizeof(int32_t) * (size_t)(entry_terms ? n_entry_terms : 0), true, false,
-             &en));
-  TRY(sg.map(replies, sizeof(mraft_ae_reply) * n, false, true, &r));
-  TRY(sg.map(results, sizeof(mraft_ae_result) * n, false, true, &rs));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
+  const mraft_ae_args *a = sg.in(args, n);
+  const int32_t *en = sg.in(entry_terms, entry_terms ? n_entry_terms : 0);
+  mraft_ae_reply *r = sg.out(replies, n);
+  mraft_ae_result *rs = sg.out(results, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
   if (en) {  // entries in a caller buffer: one message per wave, nothing is read while written
-    mraft::launch_claim(a, n, sizeof(mraft_ae_args), offsetof(mraft_ae_args, slot), nullptr, gp_of(h), h->P,
-                        h->claim, h->epoch, (int32_t *)e, h->stream);
-    mraft::launch_handle_ae_host(dev_of(h), (const mraft_ae_args *)a, n, (const int32_t *)en, n_entry_terms,
-                                 (mraft_ae_reply *)r, (int32_t *)e, (mraft_ae_result *)rs, h->stream);
+    claim(h, a, n, nullptr, e);
+    mraft::launch_handle_ae_host(dev_of(h), a, n, en, n_entry_terms, r, e, rs, h->stream);
     return sg.finish();
   }
   // Entries by reference into the engine's log: the claims with the set
   // heads, the main launch, the deferred launch — three launches, every count
   // they need stays on the device, nothing waits on the host (mraft_kernels.hip
   // "a4" for the rules).
-  if (!h->ae_total) {
-    void *t = nullptr;
-    TRY(alloc_async(h, &t, mraft::kAeTotalWords * sizeof(unsigned long long), "AppendEntries counters"));
-    h->ae_total = (unsigned long long *)t;
-    HIP_TRY(hipMemsetAsync(h->ae_total, 0, mraft::kAeTotalWords * sizeof(unsigned long long), h->stream));
-  }
-  void *sethd, *soff, *defer, *order, *stage = nullptr;
-  TRY(scratch(h, 14, sizeof(int64_t) * (size_t)n, &soff));
-  TRY(scratch(h, 15, (size_t)n, &sethd));
-  TRY(scratch(h, 18, sizeof(int64_t) * (size_t)n * mraft::kAeStripes, &defer));  // a list of n per stripe
+  if (!h->ae_total) TRY(alloc_async(h, &h->ae_total, mraft::kAeTotalWords, "AppendEntries counters", true));
+  const size_t nn = (size_t)n, L = (size_t)h->L;
+  int64_t *soff, *defer;
+  uint8_t *sethd;
+  TRY(scratch(h, kScrAeSoff, nn, &soff));
+  TRY(scratch(h, kScrAeSetHead, nn, &sethd));
+  TRY(scratch(h, kScrAeDefer, nn * mraft::kAeStripes, &defer));  // a list of n per stripe
   // the deferred launch's grid: the last call's deferred count (a pinned word
   // the device writes; a stale value only changes the grid, never a result)
-  const long long last_nd = *(volatile long long *)h->dhint;
+  const long long last_nd = hint(h, kHintDeferred);
   mraft::AeDeferBufs db{};
   const long long gmin = h->defer_grid_min;
   db.grid = (int)(last_nd < gmin ? gmin : last_nd > kDeferGridMax ? kDeferGridMax : last_nd);
   db.nslot = (int)std::min<int64_t>(db.grid, std::max<int64_t>(1, kCycSlotWords / h->L));
   // the fallback's per-item records and reader counts, its L-word buffer and
   // nslot cycle buffers
-  const size_t nn = (size_t)n, L = (size_t)h->L;
-  TRY(scratch(h, 19, nn * 16 + (1 + (size_t)db.nslot) * L * 4, &order));
-  void *kin = nullptr;
-  TRY(scratch_zeroed(h, 20, nn * 8, &kin));  // epoch-tagged: a buffer of its own, zeroed when new
+  void *order;
+  TRY(scratch_bytes(h, kScrAeOrder, nn * 16 + (1 + (size_t)db.nslot) * L * 4, &order));
+  TRY(scratch_zeroed(h, kScrAeKin, nn, &db.kin));  // epoch-tagged: a buffer of its own, zeroed when new
   db.fb = (int4 *)order;
-  db.kin = (unsigned long long *)kin;
   db.cyc = (int32_t *)(db.fb + nn);
   db.cslot = db.cyc + L;
   db.hint = h->dhint_dev;
   // MRAFT_STAGE_AUTO: a batch that exceeded the stage (its need published by
-  // the device, dhint[1]) grows it for the calls after it (stream-ordered)
+  // the device, kHintStageNeed) grows it for the calls after it (stream-ordered)
   if (h->stage_auto) {
-    const long long need = ((volatile long long *)h->dhint)[1];
-    if (need > h->stage_cap) {
-      const int64_t want = std::min<int64_t>((int64_t)INT32_MAX, (need + need / 4 + kStageStep - 1) / kStageStep * kStageStep);
-      h->stage_cap = want;
-    }
+    const long long need = hint(h, kHintStageNeed);
+    if (need > h->stage_cap)
+      h->stage_cap = std::min<int64_t>((int64_t)INT32_MAX, (need + need / 4 + kStageStep - 1) / kStageStep * kStageStep);
   }
   // the stage: when it cannot be allocated the batch runs with none (every
   // staged item then takes the ordered fallback: the same results, slower);
   // an automatic stage stops growing there
-  if (h->stage_cap > 0 && scratch(h, 16, sizeof(int32_t) * (size_t)h->stage_cap, &stage) != MRAFT_OK) {
+  int32_t *stage = nullptr;
+  if (h->stage_cap > 0 && scratch(h, kScrAeStage, (size_t)h->stage_cap, &stage) != MRAFT_OK) {
     stage = nullptr;
     h->stage_auto = false;
   }
   const int ni = h->P - 1 < 1 ? 1 : h->P - 1 > 7 ? 7 : h->P - 1;
   const int64_t n_log = gp_of(h) * h->L;
-  mraft::launch_claim_ae((const mraft_ae_args *)a, n, n_log, h->L, gp_of(h), ni, h->claim, h->srcmark, h->epoch,
-                         (int32_t *)e, (uint8_t *)sethd, h->ae_total, h->stream);
-  mraft::launch_handle_ae_ref(dev_of(h), (const mraft_ae_args *)a, n, ni, h->claim, h->srcmark, h->epoch,
-                              (int32_t *)e, (const uint8_t *)sethd, (int64_t *)soff, (int64_t *)defer, h->ae_total,
-                              (int32_t *)stage, stage ? h->stage_cap : 0, db, (mraft_ae_reply *)r,
-                              (mraft_ae_result *)rs, h->stream);
+  mraft::launch_claim_ae(a, n, n_log, h->L, gp_of(h), ni, h->claim, h->srcmark, h->epoch, e, sethd, h->ae_total,
+                         h->stream);
+  mraft::launch_handle_ae_ref(dev_of(h), a, n, ni, h->claim, h->srcmark, h->epoch, e, sethd, soff, defer, h->ae_total,
+                              stage, stage ? h->stage_cap : 0, db, r, rs, h->stream);
   return sg.finish();
 }
 
@@ -871,29 +969,15 @@ int64_t mraft_get_stage_capacity(const mraft_engine *h) { return h ? h->stage_ca
 int mraft_process_append_replies(mraft_engine *h, const mraft_ae_result *items, int64_t n,
                                  const int64_t *seg_begin, int64_t n_seg, int32_t *out_flags,
                                  int32_t *item_err, int32_t where) {
-  TRY(enter(h));
-  if (n < 0 || (n > 0 && (!items || !out_flags || !item_err)))
-    return fail(MRAFT_E_INVAL, "null argument");
-  if (seg_begin && n_seg < 0) return fail(MRAFT_E_INVAL, "n_seg < 0");
-  if (n == 0) return MRAFT_OK;
-  const int64_t ns = seg_begin ? n_seg : n;
-  HIP_TRY(hipSetDevice(h->device));
-  TRY(ensure_claim(h));
-  Stage sg(h, where);
-  void *it, *sb, *fl, *e, *se;
-  TRY(sg.map(items, sizeof(mraft_ae_result) * n, true, false, &it));
-  TRY(sg.map(seg_begin, sizeof(int64_t) * (size_t)(seg_begin ? n_seg + 1 : 0), true, false, &sb));
-  TRY(sg.map(out_flags, sizeof(int32_t) * n, false, true, &fl));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  TRY(scratch(h, 1, sizeof(int32_t) * (size_t)ns, &se));
-  void *sc;
-  TRY(scratch(h, 7, mraft::fold_scan_bytes(n, ns), &sc));
   // three launches: the segment claims with the outputs zeroed, the fold
   // (which rejects a segment whose slot another one claimed), the tail (the
   // segments longer than a lane group, and the a1 scans the probes left open)
-  mraft::launch_fold(dev_of(h), (const mraft_ae_result *)it, n, (const int64_t *)sb, ns, gp_of(h), h->claim,
-                     h->epoch, (int32_t *)se, (int32_t *)fl, (int32_t *)e, sc, h->stream);
-  return sg.finish();
+  return fold_replies(h, items, n, seg_begin, n_seg, out_flags, item_err, where, [=](const FoldBufs<mraft_ae_result> &b) -> int {
+    void *sc;
+    TRY(scratch_bytes(h, kScrFoldScan, mraft::fold_scan_bytes(n, b.ns), &sc));
+    mraft::launch_fold(dev_of(h), b.it, n, b.sb, b.ns, gp_of(h), h->claim, h->epoch, b.se, b.fl, b.e, sc, h->stream);
+    return MRAFT_OK;
+  });
 }
 
 int mraft_start(mraft_engine *h, const int32_t *slots, const int32_t *counts, int64_t n,
@@ -903,18 +987,13 @@ int mraft_start(mraft_engine *h, const int32_t *slots, const int32_t *counts, in
   if (n < 0 || (n > 0 && (!slots || !out_index || !out_term || !out_is_leader || !item_err)))
     return fail(MRAFT_E_INVAL, "null argument");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   TRY(ensure_claim(h));
   Stage sg(h, where);
-  void *s, *c, *oi, *ot, *ol, *e;
-  TRY(sg.map(slots, sizeof(int32_t) * n, true, false, &s));
-  TRY(sg.map(counts, sizeof(int32_t) * n, true, false, &c));
-  TRY(sg.map(out_index, sizeof(int32_t) * n, false, true, &oi));
-  TRY(sg.map(out_term, sizeof(int32_t) * n, false, true, &ot));
-  TRY(sg.map(out_is_leader, sizeof(int32_t) * n, false, true, &ol));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  mraft::launch_start(dev_of(h), (const int32_t *)s, (const int32_t *)c, n, (int32_t *)oi,
-                      (int32_t *)ot, (int32_t *)ol, (int32_t *)e, h->claim, h->epoch, h->stream);
+  const int32_t *s = sg.in(slots, n), *c = sg.in(counts, n);
+  int32_t *oi = sg.out(out_index, n), *ot = sg.out(out_term, n), *ol = sg.out(out_is_leader, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
+  mraft::launch_start(dev_of(h), s, c, n, oi, ot, ol, e, h->claim, h->epoch, h->stream);
   return sg.finish();
 }
 
@@ -923,14 +1002,12 @@ int mraft_collect_apply(mraft_engine *h, int32_t *out_from, int32_t *out_to, int
   TRY(enter(h));
   if (!out_from || !out_to) return fail(MRAFT_E_INVAL, "null argument");
   if (!out_snap_index != !out_snap_term) return fail(MRAFT_E_INVAL, "snapshot outputs: both or neither");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *f, *t, *si, *st;
-  TRY(sg.map(out_from, sizeof(int32_t) * gp_of(h), false, true, &f));
-  TRY(sg.map(out_to, sizeof(int32_t) * gp_of(h), false, true, &t));
-  TRY(sg.map(out_snap_index, sizeof(int32_t) * gp_of(h), false, true, &si));
-  TRY(sg.map(out_snap_term, sizeof(int32_t) * gp_of(h), false, true, &st));
-  mraft::launch_collect_apply(dev_of(h), (int32_t *)f, (int32_t *)t, (int32_t *)si, (int32_t *)st, h->stream);
+  const size_t gp = (size_t)gp_of(h);
+  int32_t *f = sg.out(out_from, gp), *t = sg.out(out_to, gp);
+  int32_t *si = sg.out(out_snap_index, gp), *st = sg.out(out_snap_term, gp);
+  TRY(sg.status());
+  mraft::launch_collect_apply(dev_of(h), f, t, si, st, h->stream);
   return sg.finish();
 }
 
@@ -941,18 +1018,13 @@ int mraft_collect_apply_compact(mraft_engine *h, int32_t *out_slots, int32_t *ou
   if (cap < 0 || !out_n || (cap > 0 && (!out_slots || !out_from || !out_to)) ||
       (!out_snap_index) != (!out_snap_term))
     return fail(MRAFT_E_INVAL, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *sl, *si, *stm, *f, *t, *n, *bc;
-  TRY(sg.map(out_slots, sizeof(int32_t) * (size_t)cap, false, true, &sl));
-  TRY(sg.map(out_snap_index, sizeof(int32_t) * (size_t)cap, false, true, &si));
-  TRY(sg.map(out_snap_term, sizeof(int32_t) * (size_t)cap, false, true, &stm));
-  TRY(sg.map(out_from, sizeof(int32_t) * (size_t)cap, false, true, &f));
-  TRY(sg.map(out_to, sizeof(int32_t) * (size_t)cap, false, true, &t));
-  TRY(sg.map(out_n, sizeof(int64_t), false, true, &n));
-  TRY(scratch(h, 6, sizeof(int32_t) * (size_t)((gp_of(h) + 255) / 256), &bc));
-  mraft::launch_collect_apply_compact(dev_of(h), (int32_t *)bc, cap, (int32_t *)sl, (int32_t *)si,
-                                      (int32_t *)stm, (int32_t *)f, (int32_t *)t, (int64_t *)n, h->stream);
+  int32_t *sl = sg.out(out_slots, cap), *si = sg.out(out_snap_index, cap), *stm = sg.out(out_snap_term, cap);
+  int32_t *f = sg.out(out_from, cap), *t = sg.out(out_to, cap), *bc;
+  int64_t *total = sg.out(out_n, 1);
+  TRY(sg.status());
+  TRY(scratch(h, kScrApplyBlocks, (size_t)((gp_of(h) + 255) / 256), &bc));
+  mraft::launch_collect_apply_compact(dev_of(h), bc, cap, sl, si, stm, f, t, total, h->stream);
   return sg.finish();
 }
 
@@ -961,16 +1033,13 @@ int mraft_snapshot(mraft_engine *h, const int32_t *slots, const int32_t *index, 
   TRY(enter(h));
   if (n < 0 || (n > 0 && (!slots || !index || !item_err))) return fail(MRAFT_E_INVAL, "null argument");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   TRY(ensure_claim(h));
   Stage sg(h, where);
-  void *s, *x, *e;
-  TRY(sg.map(slots, sizeof(int32_t) * n, true, false, &s));
-  TRY(sg.map(index, sizeof(int32_t) * n, true, false, &x));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  mraft::launch_claim(s, n, sizeof(int32_t), 0, nullptr, gp_of(h), h->P, h->claim, h->epoch,
-                      (int32_t *)e, h->stream);
-  mraft::launch_snapshot(dev_of(h), (const int32_t *)s, (const int32_t *)x, n, (int32_t *)e, h->stream);
+  const int32_t *s = sg.in(slots, n), *x = sg.in(index, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
+  claim(h, s, n, nullptr, e);
+  mraft::launch_snapshot(dev_of(h), s, x, n, e, h->stream);
   return sg.finish();
 }
 
@@ -981,15 +1050,12 @@ int mraft_gather_install_snapshot_args(mraft_engine *h, const int32_t *slots, co
   if (n < 0 || (n > 0 && (!slots || !peers || !out_args || !item_err)))
     return fail(MRAFT_E_INVAL, "null argument");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *s, *p, *o, *e;
-  TRY(sg.map(slots, sizeof(int32_t) * n, true, false, &s));
-  TRY(sg.map(peers, sizeof(int32_t) * n, true, false, &p));
-  TRY(sg.map(out_args, sizeof(mraft_is_args) * n, false, true, &o));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  mraft::launch_gather_is(dev_of(h), (const int32_t *)s, (const int32_t *)p, n, (mraft_is_args *)o,
-                          (int32_t *)e, h->stream);
+  const int32_t *s = sg.in(slots, n), *p = sg.in(peers, n);
+  mraft_is_args *o = sg.out(out_args, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
+  mraft::launch_gather_is(dev_of(h), s, p, n, o, e, h->stream);
   return sg.finish();
 }
 
@@ -1000,47 +1066,21 @@ int mraft_handle_install_snapshot(mraft_engine *h, const mraft_is_args *args, in
   if (n < 0 || (n > 0 && (!args || !replies || !out_flags || !item_err)))
     return fail(MRAFT_E_INVAL, "null argument");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   TRY(ensure_claim(h));
   Stage sg(h, where);
-  void *a, *r, *f, *e;
-  TRY(sg.map(args, sizeof(mraft_is_args) * n, true, false, &a));
-  TRY(sg.map(replies, sizeof(mraft_is_reply) * n, false, true, &r));
-  TRY(sg.map(out_flags, sizeof(int32_t) * n, false, true, &f));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  mraft::launch_claim(a, n, sizeof(mraft_is_args), offsetof(mraft_is_args, slot), nullptr, gp_of(h),
-                      h->P, h->claim, h->epoch, (int32_t *)e, h->stream);
-  mraft::launch_handle_is(dev_of(h), (const mraft_is_args *)a, n, (mraft_is_reply *)r, (int32_t *)f,
-                          (int32_t *)e, h->stream);
+  const mraft_is_args *a = sg.in(args, n);
+  mraft_is_reply *r = sg.out(replies, n);
+  int32_t *f = sg.out(out_flags, n), *e = sg.out(item_err, n);
+  TRY(sg.status());
+  claim(h, a, n, nullptr, e);
+  mraft::launch_handle_is(dev_of(h), a, n, r, f, e, h->stream);
   return sg.finish();
 }
 
 int mraft_process_install_snapshot_replies(mraft_engine *h, const mraft_is_result *items, int64_t n,
                                            const int64_t *seg_begin, int64_t n_seg,
                                            int32_t *out_flags, int32_t *item_err, int32_t where) {
-  TRY(enter(h));
-  if (n < 0 || (n > 0 && (!items || !out_flags || !item_err)))
-    return fail(MRAFT_E_INVAL, "null argument");
-  if (seg_begin && n_seg < 0) return fail(MRAFT_E_INVAL, "n_seg < 0");
-  if (n == 0) return MRAFT_OK;
-  const int64_t ns = seg_begin ? n_seg : n;
-  HIP_TRY(hipSetDevice(h->device));
-  TRY(ensure_claim(h));
-  Stage sg(h, where);
-  void *it, *sb, *fl, *e, *se;
-  TRY(sg.map(items, sizeof(mraft_is_result) * n, true, false, &it));
-  TRY(sg.map(seg_begin, sizeof(int64_t) * (size_t)(seg_begin ? n_seg + 1 : 0), true, false, &sb));
-  TRY(sg.map(out_flags, sizeof(int32_t) * n, false, true, &fl));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  TRY(scratch(h, 1, sizeof(int32_t) * (size_t)ns, &se));
-  HIP_TRY(hipMemsetAsync(fl, 0, sizeof(int32_t) * n, h->stream));
-  HIP_TRY(hipMemsetAsync(e, 0, sizeof(int32_t) * n, h->stream));
-  mraft::launch_claim(it, ns, sizeof(mraft_is_result), offsetof(mraft_is_result, slot),
-                      (const int64_t *)sb, gp_of(h), h->P, h->claim, h->epoch, (int32_t *)se,
-                      h->stream);
-  mraft::launch_process_is(dev_of(h), (const mraft_is_result *)it, n, (const int64_t *)sb, ns,
-                           (int32_t *)se, (int32_t *)fl, (int32_t *)e, h->stream);
-  return sg.finish();
+  return fold_records(h, items, n, seg_begin, n_seg, out_flags, item_err, where, mraft::launch_process_is);
 }
 
 int mraft_start_election(mraft_engine *h, const int32_t *slots, int64_t n, mraft_rv_args *out_args,
@@ -1049,17 +1089,14 @@ int mraft_start_election(mraft_engine *h, const int32_t *slots, int64_t n, mraft
   if (n < 0 || (n > 0 && (!slots || !out_args || !item_err)))
     return fail(MRAFT_E_INVAL, "null argument");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   TRY(ensure_claim(h));
   Stage sg(h, where);
-  void *s, *o, *e;
-  TRY(sg.map(slots, sizeof(int32_t) * n, true, false, &s));
-  TRY(sg.map(out_args, sizeof(mraft_rv_args) * n, false, true, &o));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  mraft::launch_claim(s, n, sizeof(int32_t), 0, nullptr, gp_of(h), h->P, h->claim, h->epoch,
-                      (int32_t *)e, h->stream);
-  mraft::launch_start_election(dev_of(h), (const int32_t *)s, n, (mraft_rv_args *)o, (int32_t *)e,
-                               h->stream);
+  const int32_t *s = sg.in(slots, n);
+  mraft_rv_args *o = sg.out(out_args, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
+  claim(h, s, n, nullptr, e);
+  mraft::launch_start_election(dev_of(h), s, n, o, e, h->stream);
   return sg.finish();
 }
 
@@ -1069,58 +1106,32 @@ int mraft_handle_request_vote(mraft_engine *h, const mraft_rv_args *args, int64_
   if (n < 0 || (n > 0 && (!args || !replies || !item_err)))
     return fail(MRAFT_E_INVAL, "null argument");
   if (n == 0) return MRAFT_OK;
-  HIP_TRY(hipSetDevice(h->device));
   TRY(ensure_claim(h));
   Stage sg(h, where);
-  void *a, *r, *e;
-  TRY(sg.map(args, sizeof(mraft_rv_args) * n, true, false, &a));
-  TRY(sg.map(replies, sizeof(mraft_rv_reply) * n, false, true, &r));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  mraft::launch_claim(a, n, sizeof(mraft_rv_args), offsetof(mraft_rv_args, slot), nullptr, gp_of(h),
-                      h->P, h->claim, h->epoch, (int32_t *)e, h->stream);
-  mraft::launch_handle_rv(dev_of(h), (const mraft_rv_args *)a, n, (mraft_rv_reply *)r, (int32_t *)e,
-                          h->stream);
+  const mraft_rv_args *a = sg.in(args, n);
+  mraft_rv_reply *r = sg.out(replies, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
+  claim(h, a, n, nullptr, e);
+  mraft::launch_handle_rv(dev_of(h), a, n, r, e, h->stream);
   return sg.finish();
 }
 
 int mraft_process_vote_replies(mraft_engine *h, const mraft_rv_result *items, int64_t n,
                                const int64_t *seg_begin, int64_t n_seg, int32_t *out_flags,
                                int32_t *item_err, int32_t where) {
-  TRY(enter(h));
-  if (n < 0 || (n > 0 && (!items || !out_flags || !item_err)))
-    return fail(MRAFT_E_INVAL, "null argument");
-  if (seg_begin && n_seg < 0) return fail(MRAFT_E_INVAL, "n_seg < 0");
-  if (n == 0) return MRAFT_OK;
-  const int64_t ns = seg_begin ? n_seg : n;
-  HIP_TRY(hipSetDevice(h->device));
-  TRY(ensure_claim(h));
-  Stage sg(h, where);
-  void *it, *sb, *fl, *e, *se;
-  TRY(sg.map(items, sizeof(mraft_rv_result) * n, true, false, &it));
-  TRY(sg.map(seg_begin, sizeof(int64_t) * (size_t)(seg_begin ? n_seg + 1 : 0), true, false, &sb));
-  TRY(sg.map(out_flags, sizeof(int32_t) * n, false, true, &fl));
-  TRY(sg.map(item_err, sizeof(int32_t) * n, false, true, &e));
-  TRY(scratch(h, 1, sizeof(int32_t) * (size_t)ns, &se));
-  HIP_TRY(hipMemsetAsync(fl, 0, sizeof(int32_t) * n, h->stream));
-  HIP_TRY(hipMemsetAsync(e, 0, sizeof(int32_t) * n, h->stream));
-  mraft::launch_claim(it, ns, sizeof(mraft_rv_result), offsetof(mraft_rv_result, slot),
-                      (const int64_t *)sb, gp_of(h), h->P, h->claim, h->epoch, (int32_t *)se,
-                      h->stream);
-  mraft::launch_tally(dev_of(h), (const mraft_rv_result *)it, n, (const int64_t *)sb, ns,
-                      (int32_t *)se, (int32_t *)fl, (int32_t *)e, h->stream);
-  return sg.finish();
+  return fold_records(h, items, n, seg_begin, n_seg, out_flags, item_err, where, mraft::launch_tally);
 }
 
 int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask, int32_t rounds,
                           int32_t *group_flags, int32_t where) {
   TRY(enter(h));
   if (!cand_mask || rounds < 0) return fail(MRAFT_E_INVAL, "null mask or negative rounds");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *m, *gf;
-  TRY(sg.map(cand_mask, (size_t)rounds * h->G, true, false, &m));
-  TRY(sg.map(group_flags, sizeof(int32_t) * h->G, false, true, &gf));
-  mraft::launch_election_rounds(dev_of(h), (const uint8_t *)m, rounds, (int32_t *)gf, h->stream);
+  const uint8_t *m = sg.in(cand_mask, (size_t)rounds * h->G);
+  int32_t *gf = sg.out(group_flags, h->G);
+  TRY(sg.status());
+  mraft::launch_election_rounds(dev_of(h), m, rounds, gf, h->stream);
   return sg.finish();
 }
 
@@ -1129,11 +1140,6 @@ int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask, int32_t rou
 }  // extern "C"
 
 namespace {
-
-// Scratch slots of the clock step and the ticker (Stage maps from slot 8 up,
-// the message path owns 14-20).
-constexpr size_t kScrClockLp = 24, kScrClockGf = 25, kScrClockCommit = 26, kScrClockTl = 27, kScrClockTg = 28,
-                 kScrTickerCnt = 29;
 
 int check_now(int32_t now) {
   if (now < 0 || now > mraft::kTimerNowMax) return fail(MRAFT_E_INVAL, "now = %d outside [0, 2^30]", now);
@@ -1165,18 +1171,17 @@ int mraft_timers_enable(mraft_engine *h, const mraft_timer_config *cfg, int32_t 
   // The arrays reach the handle only when both allocations and the arming
   // launch succeeded; until then they are locals, freed on failure. A second
   // enable re-arms the arrays the handle already has.
-  void *ed = h->tm_ed, *hd = h->tm_hd;
+  int32_t *ed = h->tm_ed, *hd = h->tm_hd;
   const bool fresh = !h->tm_ed;
-  const size_t b = (size_t)gp_of(h) * sizeof(int32_t);
   if (fresh) {
-    TRY(alloc_async(h, &ed, b, "election_due"));
-    const int rc = alloc_async(h, &hd, b, "heartbeat_due");
+    TRY(alloc_async(h, &ed, (size_t)gp_of(h), "election_due"));
+    const int rc = alloc_async(h, &hd, (size_t)gp_of(h), "heartbeat_due");
     if (rc) {
       (void)hipFreeAsync(ed, h->stream);
       return rc;
     }
   }
-  mraft::launch_timers_arm_all(mraft::TimerDev{(int32_t *)ed, (int32_t *)hd, *cfg}, gp_of(h), now, h->stream);
+  mraft::launch_timers_arm_all(mraft::TimerDev{ed, hd, *cfg}, gp_of(h), now, h->stream);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     if (fresh) {
@@ -1185,8 +1190,8 @@ int mraft_timers_enable(mraft_engine *h, const mraft_timer_config *cfg, int32_t 
     }
     return fail(MRAFT_E_HIP, "arming the timers failed: %s", hipGetErrorString(e));
   }
-  h->tm_ed = (int32_t *)ed;
-  h->tm_hd = (int32_t *)hd;
+  h->tm_ed = ed;
+  h->tm_hd = hd;
   h->tcfg = *cfg;
   return MRAFT_OK;
 }
@@ -1203,23 +1208,19 @@ int mraft_timers_disable(mraft_engine *h) {
 int mraft_timers_load(mraft_engine *h, const mraft_timers_soa *src, int32_t where) {
   TRY(enter_timers(h));
   if (!src) return fail(MRAFT_E_INVAL, "src is null");
-  const hipMemcpyKind k = where == MRAFT_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   const size_t b = (size_t)gp_of(h) * sizeof(int32_t);
-  if (src->election_due) HIP_TRY(hipMemcpyAsync(h->tm_ed, src->election_due, b, k, h->stream));
-  if (src->heartbeat_due) HIP_TRY(hipMemcpyAsync(h->tm_hd, src->heartbeat_due, b, k, h->stream));
-  if (where == MRAFT_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
-  return MRAFT_OK;
+  TRY(copy_array(h, true, h->tm_ed, src->election_due, b, where));
+  TRY(copy_array(h, true, h->tm_hd, src->heartbeat_due, b, where));
+  return finish_copies(h, where);
 }
 
 int mraft_timers_store(mraft_engine *h, const mraft_timers_soa *dst, int32_t where) {
   TRY(enter_timers(h));
   if (!dst) return fail(MRAFT_E_INVAL, "dst is null");
-  const hipMemcpyKind k = where == MRAFT_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   const size_t b = (size_t)gp_of(h) * sizeof(int32_t);
-  if (dst->election_due) HIP_TRY(hipMemcpyAsync(dst->election_due, h->tm_ed, b, k, h->stream));
-  if (dst->heartbeat_due) HIP_TRY(hipMemcpyAsync(dst->heartbeat_due, h->tm_hd, b, k, h->stream));
-  if (where == MRAFT_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
-  return MRAFT_OK;
+  TRY(copy_array(h, false, h->tm_ed, dst->election_due, b, where));
+  TRY(copy_array(h, false, h->tm_hd, dst->heartbeat_due, b, where));
+  return finish_copies(h, where);
 }
 
 int mraft_timers_arm(mraft_engine *h, const int32_t *slots, int64_t n, int32_t now, int32_t where) {
@@ -1228,9 +1229,9 @@ int mraft_timers_arm(mraft_engine *h, const int32_t *slots, int64_t n, int32_t n
   TRY(check_now(now));
   if (n == 0) return MRAFT_OK;
   Stage sg(h, where);
-  void *s;
-  TRY(sg.map(slots, sizeof(int32_t) * (size_t)n, true, false, &s));
-  mraft::launch_timers_arm(timers_of(h), (const int32_t *)s, n, gp_of(h), now, h->stream);
+  const int32_t *s = sg.in(slots, n);
+  TRY(sg.status());
+  mraft::launch_timers_arm(timers_of(h), s, n, gp_of(h), now, h->stream);
   return sg.finish();
 }
 
@@ -1245,14 +1246,12 @@ int mraft_ticker(mraft_engine *h, int32_t now, int32_t *out_election_slots, int6
   cap_e = std::min<int64_t>(cap_e, gp_of(h));
   cap_h = std::min<int64_t>(cap_h, gp_of(h));
   Stage sg(h, where);
-  void *oe, *oh, *ne, *nh, *bc;
-  TRY(sg.map(cap_e ? out_election_slots : nullptr, sizeof(int32_t) * (size_t)cap_e, false, true, &oe));
-  TRY(sg.map(cap_h ? out_heartbeat_slots : nullptr, sizeof(int32_t) * (size_t)cap_h, false, true, &oh));
-  TRY(sg.map(out_n_e, sizeof(int64_t), false, true, &ne));
-  TRY(sg.map(out_n_h, sizeof(int64_t), false, true, &nh));
-  TRY(scratch(h, kScrTickerCnt, sizeof(int32_t) * 2 * (size_t)mraft::ticker_blocks(gp_of(h)), &bc));
-  mraft::launch_ticker(dev_of(h), timers_of(h), now, (int32_t *)bc, (int32_t *)oe, cap_e, (int64_t *)ne,
-                       (int32_t *)oh, cap_h, (int64_t *)nh, h->stream);
+  int32_t *oe = sg.out(cap_e ? out_election_slots : nullptr, cap_e);
+  int32_t *oh = sg.out(cap_h ? out_heartbeat_slots : nullptr, cap_h), *bc;
+  int64_t *ne = sg.out(out_n_e, 1), *nh = sg.out(out_n_h, 1);
+  TRY(sg.status());
+  TRY(scratch(h, kScrTickerCnt, 2 * (size_t)mraft::ticker_blocks(gp_of(h)), &bc));
+  mraft::launch_ticker(dev_of(h), timers_of(h), now, bc, oe, cap_e, ne, oh, cap_h, nh, h->stream);
   return sg.finish();
 }
 
@@ -1273,11 +1272,11 @@ int mraft_timers_note(mraft_engine *h, int32_t kind, const void *records, const 
   TRY(check_now(now));
   if (n == 0) return MRAFT_OK;
   Stage sg(h, where);
-  void *r, *o, *e;
-  TRY(sg.map(records, rb * (size_t)n, true, false, &r));
-  TRY(sg.map(outcome, ob * (size_t)n, true, false, &o));
-  TRY(sg.map(item_err, sizeof(int32_t) * (size_t)n, true, false, &e));
-  mraft::launch_timers_note(timers_of(h), kind, r, o, (const int32_t *)e, n, gp_of(h), now, h->stream);
+  // records and outcomes of the kind's types: staged as bytes
+  const char *r = sg.in((const char *)records, rb * (size_t)n), *o = sg.in((const char *)outcome, ob * (size_t)n);
+  const int32_t *e = sg.in(item_err, n);
+  TRY(sg.status());
+  mraft::launch_timers_note(timers_of(h), kind, r, o, e, n, gp_of(h), now, h->stream);
   return sg.finish();
 }
 
@@ -1288,32 +1287,33 @@ int mraft_clock_step(mraft_engine *h, int32_t now, uint32_t flags, uint8_t *cand
   if (flags & ~(uint32_t)MRAFT_CLOCK_SEND_ALL) return fail(MRAFT_E_INVAL, "unknown flags 0x%x", flags);
   TRY(check_now(now));
   Stage sg(h, where);
-  const size_t gb = sizeof(int32_t) * (size_t)h->G;
-  void *cm, *ef, *tg;
+  const size_t G = (size_t)h->G;
   // the words one launch hands to the next live in the caller's buffer when
   // there is one, in the engine's scratch otherwise
-  void *need[4];
+  int32_t *need[4], *tg;
   int32_t *const outs[4] = {leader_peer, group_flags, commit, term_leader};
-  const size_t slots[4] = {kScrClockLp, kScrClockGf, kScrClockCommit, kScrClockTl};
+  const ScratchSlot slots[4] = {kScrClockLp, kScrClockGf, kScrClockCommit, kScrClockTl};
   for (int k = 0; k < 4; ++k) {
     if (outs[k])
-      TRY(sg.map(outs[k], gb, false, true, &need[k]));
+      need[k] = sg.out(outs[k], G);
     else
-      TRY(scratch(h, slots[k], gb, &need[k]));
+      TRY(scratch(h, slots[k], G, &need[k]));
+    TRY(sg.status());
   }
-  TRY(sg.map(cand_mask, (size_t)h->G, false, true, &cm));
-  TRY(sg.map(election_flags, gb, false, true, &ef));
-  TRY(scratch(h, kScrClockTg, gb, &tg));
-  int32_t *lp = (int32_t *)need[0], *gf = (int32_t *)need[1];
+  uint8_t *cm = sg.out(cand_mask, G);
+  int32_t *ef = sg.out(election_flags, G);
+  TRY(sg.status());
+  TRY(scratch(h, kScrClockTg, G, &tg));
+  int32_t *lp = need[0], *gf = need[1];
   const mraft::TimerDev t = timers_of(h);
   // A-C: ticker, one election round, the sender
-  mraft::launch_clock_round(dev_of(h), t, now, flags, (uint8_t *)cm, lp, (int32_t *)tg, (int32_t *)ef, h->stream);
+  mraft::launch_clock_round(dev_of(h), t, now, flags, cm, lp, tg, ef, h->stream);
   // D: the tick, under the handle's mode and shards
-  TRY(launch_tick(h, lp, gf, (int32_t *)need[2], (int32_t *)need[3]));
+  TRY(launch_tick(h, lp, gf, need[2], need[3]));
   // E: the tick's resets, on the engine stream after every shard (a
   // device-side wait)
   TRY(join_shards(h));
-  mraft::launch_clock_resets(dev_of(h), t, now, gf, lp, (const int32_t *)tg, h->stream);
+  mraft::launch_clock_resets(dev_of(h), t, now, gf, lp, tg, h->stream);
   return sg.finish();
 }
 
@@ -1322,11 +1322,10 @@ int mraft_clock_step(mraft_engine *h, int32_t now, uint32_t flags, uint8_t *cand
 int mraft_collect_persist(mraft_engine *h, int32_t *out_bits, int32_t where) {
   TRY(enter(h));
   if (!out_bits) return fail(MRAFT_E_INVAL, "out_bits is null");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *o;
-  TRY(sg.map(out_bits, sizeof(int32_t) * (size_t)gp_of(h), false, true, &o));
-  mraft::launch_collect_persist(dev_of(h), (int32_t *)o, h->stream);
+  int32_t *o = sg.out(out_bits, (size_t)gp_of(h));
+  TRY(sg.status());
+  mraft::launch_collect_persist(dev_of(h), o, h->stream);
   return sg.finish();
 }
 
@@ -1337,12 +1336,12 @@ int mraft_read_persistent(mraft_engine *h, const int32_t *slots, int64_t n, mraf
   if (n == 0) return MRAFT_OK;
   for (int64_t i = 0; i < n; ++i)
     if (slots[i] < 0 || slots[i] >= gp_of(h)) return fail(MRAFT_E_INVAL, "slot %d out of range", slots[i]);
-  HIP_TRY(hipSetDevice(h->device));
-  void *ds, *dh, *dt;
-  TRY(scratch(h, 2, sizeof(int32_t) * (size_t)n, &ds));
-  TRY(scratch(h, 3, sizeof(mraft_persistent) * (size_t)n, &dh));
+  int32_t *ds, *dt;
+  mraft_persistent *dh;
+  TRY(scratch(h, kScrPersistSlots, (size_t)n, &ds));
+  TRY(scratch(h, kScrPersistHdr, (size_t)n, &dh));
   HIP_TRY(hipMemcpyAsync(ds, slots, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-  mraft::launch_read_persistent_hdr(dev_of(h), (const int32_t *)ds, n, (mraft_persistent *)dh, h->stream);
+  mraft::launch_read_persistent_hdr(dev_of(h), ds, n, dh, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, dh, sizeof(mraft_persistent) * n, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1354,10 +1353,9 @@ int mraft_read_persistent(mraft_engine *h, const int32_t *slots, int64_t n, mraf
   if (!out_terms || terms_cap < off)
     return fail(MRAFT_E_INVAL, "read_persistent: %lld terms needed, capacity %lld", (long long)off,
                 (long long)terms_cap);
-  TRY(scratch(h, 4, sizeof(int32_t) * (size_t)off, &dt));
+  TRY(scratch(h, kScrPersistTerms, (size_t)off, &dt));
   HIP_TRY(hipMemcpyAsync(dh, out, sizeof(mraft_persistent) * n, hipMemcpyHostToDevice, h->stream));
-  mraft::launch_read_persistent_terms(dev_of(h), (const mraft_persistent *)dh, n, (int32_t *)dt,
-                                      h->stream);
+  mraft::launch_read_persistent_terms(dev_of(h), dh, n, dt, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_terms, dt, sizeof(int32_t) * off, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1385,17 +1383,16 @@ int mraft_restore(mraft_engine *h, const mraft_persistent *in, int64_t n, const 
     if (e == MRAFT_ITEM_OK) seen[(size_t)r.slot] = 1;
     item_err[i] = e;
   }
-  HIP_TRY(hipSetDevice(h->device));
-  void *dh, *dt, *de;
-  TRY(scratch(h, 3, sizeof(mraft_persistent) * (size_t)n, &dh));
-  TRY(scratch(h, 4, sizeof(int32_t) * (size_t)(n_terms > 0 ? n_terms : 1), &dt));
-  TRY(scratch(h, 5, sizeof(int32_t) * (size_t)n, &de));
+  mraft_persistent *dh;
+  int32_t *dt, *de;
+  TRY(scratch(h, kScrPersistHdr, (size_t)n, &dh));
+  TRY(scratch(h, kScrPersistTerms, (size_t)(n_terms > 0 ? n_terms : 1), &dt));
+  TRY(scratch(h, kScrRestoreErr, (size_t)n, &de));
   HIP_TRY(hipMemcpyAsync(dh, in, sizeof(mraft_persistent) * n, hipMemcpyHostToDevice, h->stream));
   if (n_terms > 0)
     HIP_TRY(hipMemcpyAsync(dt, terms, sizeof(int32_t) * n_terms, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(de, item_err, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-  mraft::launch_restore(dev_of(h), (const mraft_persistent *)dh, n, (const int32_t *)dt,
-                        (const int32_t *)de, h->stream);
+  mraft::launch_restore(dev_of(h), dh, n, dt, de, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   return MRAFT_OK;
@@ -1405,13 +1402,11 @@ int mraft_export_group_status(mraft_engine *h, const int32_t *leader_peer, int32
                               int32_t *term_leader, int32_t where) {
   TRY(enter(h));
   if (!commit || !term_leader) return fail(MRAFT_E_INVAL, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
   Stage sg(h, where);
-  void *lp, *c, *t;
-  TRY(sg.map(leader_peer, sizeof(int32_t) * h->G, true, false, &lp));
-  TRY(sg.map(commit, sizeof(int32_t) * h->G, false, true, &c));
-  TRY(sg.map(term_leader, sizeof(int32_t) * h->G, false, true, &t));
-  mraft::launch_export(dev_of(h), (const int32_t *)lp, (int32_t *)c, (int32_t *)t, h->stream);
+  const int32_t *lp = sg.in(leader_peer, h->G);
+  int32_t *c = sg.out(commit, h->G), *t = sg.out(term_leader, h->G);
+  TRY(sg.status());
+  mraft::launch_export(dev_of(h), lp, c, t, h->stream);
   return sg.finish();
 }
 
@@ -1486,9 +1481,9 @@ int mraft_allgather_status(mraft_engine *h, void *comm, const int32_t *local, in
   const size_t words = 2 * (size_t)h->G;
   if (where == MRAFT_HOST) {
     Stage sg(h, where);
-    void *l, *g;
-    TRY(sg.map(local, sizeof(int32_t) * words, true, false, &l));
-    TRY(sg.map(gathered, sizeof(int32_t) * words * nranks, false, true, &g));
+    const int32_t *l = sg.in(local, words);
+    int32_t *g = sg.out(gathered, words * nranks);
+    TRY(sg.status());
     NCCL_TRY(ncclAllGather(l, g, words, ncclInt32, c, h->stream));
     return sg.finish();
   }
@@ -1602,7 +1597,7 @@ int64_t mraft_tick_light_fallbacks(mraft_engine *h) {
   if (!h) return -1;
   long long t = 0;
   for (int s = 0; s < std::max(1, (int)h->nshards); ++s) {
-    const long long v = ((volatile long long *)h->dhint)[kHintLite + s];
+    const long long v = hint(h, kHintLite + s);
     if (v < 0) return -1;
     t += v;
   }

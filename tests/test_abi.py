@@ -76,12 +76,14 @@ def test_persistent_codec_round_trip_host_only():
 def test_message_calls_reject_bad_arguments_gpu():
     """The message-path entry points check their arguments before any launch:
     a negative item count, a null output, a negative entry-word count with a
-    caller buffer, n_seg < 0, a stage capacity outside [0, 2^31) — each
-    MRAFT_E_INVAL with a message, and the engine ticks on afterwards."""
+    caller buffer, n_seg < 0 (each of the three folds), the same for the
+    snapshot, election and vote handlers, a stage capacity outside [0, 2^31)
+    — each MRAFT_E_INVAL with a message, and the engine ticks on afterwards."""
     import numpy as np
     from oracle_lib import Oracle, assert_states_equal
     from multiraft_amd import Engine, synth_tick_state
-    from multiraft_amd._abi import AE_ARGS, AE_REPLY, AE_RESULT, HOST, ptr
+    from multiraft_amd._abi import (AE_ARGS, AE_REPLY, AE_RESULT, HOST, IS_ARGS, IS_REPLY, IS_RESULT, RV_ARGS,
+                                    RV_REPLY, RV_RESULT, ptr)
     lib = _abi.lib()
     G, P, L = 8, 3, 16
     st, lp, _ = synth_tick_state(G, P, L, seed=7)
@@ -99,6 +101,42 @@ def test_message_calls_reject_bad_arguments_gpu():
         assert b"n_entry_terms" in lib.mraft_last_error_string()
         assert lib.mraft_process_append_replies(h, ptr(res), 2, ptr(seg), -1, ptr(fl), ptr(err), HOST) == _abi.E_INVAL
         assert lib.mraft_process_append_replies(h, ptr(res), -2, None, 0, ptr(fl), ptr(err), HOST) == _abi.E_INVAL
+
+        def rejected(rc, text=b"null argument"):
+            assert rc == _abi.E_INVAL and text in lib.mraft_last_error_string()
+
+        # the three folds share one prologue: negative n, a null output, and
+        # n_seg < 0 with seg_begin given
+        for fold, dt in ((lib.mraft_process_append_replies, AE_RESULT),
+                         (lib.mraft_process_install_snapshot_replies, IS_RESULT),
+                         (lib.mraft_process_vote_replies, RV_RESULT)):
+            it = np.zeros(2, dt)
+            rejected(fold(h, ptr(it), -1, None, 0, ptr(fl), ptr(err), HOST))
+            rejected(fold(h, ptr(it), 2, None, 0, None, ptr(err), HOST))
+            rejected(fold(h, ptr(it), 2, None, 0, ptr(fl), None, HOST))
+            rejected(fold(h, None, 2, None, 0, ptr(fl), ptr(err), HOST))
+            rejected(fold(h, ptr(it), 2, ptr(seg), -1, ptr(fl), ptr(err), HOST), b"n_seg")
+        # the four claim-then-launch handlers: null and negative-n cases
+        sl, ix = np.zeros(2, np.int32), np.zeros(2, np.int32)
+        isa, isr = np.zeros(2, IS_ARGS), np.zeros(2, IS_REPLY)
+        rva, rvr = np.zeros(2, RV_ARGS), np.zeros(2, RV_REPLY)
+        rejected(lib.mraft_snapshot(h, ptr(sl), ptr(ix), -1, ptr(err), HOST))
+        rejected(lib.mraft_snapshot(h, None, ptr(ix), 2, ptr(err), HOST))
+        rejected(lib.mraft_snapshot(h, ptr(sl), None, 2, ptr(err), HOST))
+        rejected(lib.mraft_snapshot(h, ptr(sl), ptr(ix), 2, None, HOST))
+        rejected(lib.mraft_start_election(h, ptr(sl), -1, ptr(rva), ptr(err), HOST))
+        rejected(lib.mraft_start_election(h, None, 2, ptr(rva), ptr(err), HOST))
+        rejected(lib.mraft_start_election(h, ptr(sl), 2, None, ptr(err), HOST))
+        rejected(lib.mraft_start_election(h, ptr(sl), 2, ptr(rva), None, HOST))
+        rejected(lib.mraft_handle_install_snapshot(h, ptr(isa), -1, ptr(isr), ptr(fl), ptr(err), HOST))
+        rejected(lib.mraft_handle_install_snapshot(h, None, 2, ptr(isr), ptr(fl), ptr(err), HOST))
+        rejected(lib.mraft_handle_install_snapshot(h, ptr(isa), 2, None, ptr(fl), ptr(err), HOST))
+        rejected(lib.mraft_handle_install_snapshot(h, ptr(isa), 2, ptr(isr), None, ptr(err), HOST))
+        rejected(lib.mraft_handle_install_snapshot(h, ptr(isa), 2, ptr(isr), ptr(fl), None, HOST))
+        rejected(lib.mraft_handle_request_vote(h, ptr(rva), -1, ptr(rvr), ptr(err), HOST))
+        rejected(lib.mraft_handle_request_vote(h, None, 2, ptr(rvr), ptr(err), HOST))
+        rejected(lib.mraft_handle_request_vote(h, ptr(rva), 2, None, ptr(err), HOST))
+        rejected(lib.mraft_handle_request_vote(h, ptr(rva), 2, ptr(rvr), None, HOST))
         assert lib.mraft_set_stage_capacity(h, -2) == _abi.E_INVAL
         assert lib.mraft_set_stage_capacity(h, 1 << 31) == _abi.E_INVAL
         assert lib.mraft_get_stage_capacity(h) == 4 << 20  # unchanged default
