@@ -118,7 +118,7 @@ struct mraft_engine {
   unsigned long long *claim = nullptr;
   uint32_t *srcmark = nullptr;             // per slot: epoch of the last call that read its row
   uint32_t epoch = 0;
-  unsigned long long *ae_total = nullptr;  // AppendEntries by reference: the deferred launch's counters (mraft_kernels.hip)
+  unsigned long long *ae_total = nullptr;  // AppendEntries by reference: the deferred launch's counters (mraft_handle_ae.hip)
   int64_t stage_cap = kDefaultStageWords;  // words of staged entries the deferred launch may use
   bool stage_auto = true;                  // MRAFT_STAGE_AUTO: grow stage_cap to the last overflow's need
   volatile long long *dhint = nullptr;  // the pinned host words (Hint): device-written
@@ -903,7 +903,7 @@ int mraft_handle_append_entries_ex(mraft_engine *h, const mraft_ae_args *args, i
   }
   // Entries by reference into the engine's log: the claims with the set
   // heads, the main launch, the deferred launch — three launches, every count
-  // they need stays on the device, nothing waits on the host (mraft_kernels.hip
+  // they need stays on the device, nothing waits on the host (mraft_handle_ae.hip
   // "a4" for the rules).
   if (!h->ae_total) TRY(alloc_async(h, &h->ae_total, mraft::kAeTotalWords, "AppendEntries counters", true));
   const size_t nn = (size_t)n, L = (size_t)h->L;

@@ -316,17 +316,15 @@ __global__ __launch_bounds__(256) void k_clock_resets(Dev s, TimerDev t, int now
   if (hit) t.ed[sl] = election_deadline(t, sl, now);
 }
 
-unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 void launch_timers_arm_all(const TimerDev &t, int64_t gp, int32_t now, hipStream_t st) {
-  hipLaunchKernelGGL(k_timers_arm_all, dim3(blocks256(gp)), dim3(256), 0, st, t, gp, now);
+  hipLaunchKernelGGL(k_timers_arm_all, dim3(blocks_for(gp)), dim3(256), 0, st, t, gp, now);
 }
 
 void launch_timers_arm(const TimerDev &t, const int32_t *slots, int64_t n, int64_t gp, int32_t now,
                        hipStream_t st) {
-  hipLaunchKernelGGL(k_timers_arm, dim3(blocks256(n)), dim3(256), 0, st, t, slots, n, gp, now);
+  hipLaunchKernelGGL(k_timers_arm, dim3(blocks_for(n)), dim3(256), 0, st, t, slots, n, gp, now);
 }
 
 void launch_ticker(const Dev &s, const TimerDev &t, int32_t now, int32_t *bcnt, int32_t *oe, int64_t cap_e,
@@ -340,26 +338,21 @@ void launch_ticker(const Dev &s, const TimerDev &t, int32_t now, int32_t *bcnt, 
 
 void launch_timers_note(const TimerDev &t, int kind, const void *records, const void *outcome,
                         const int32_t *item_err, int64_t n, int64_t gp, int32_t now, hipStream_t st) {
-  hipLaunchKernelGGL(k_timers_note, dim3(blocks256(n)), dim3(256), 0, st, t, kind, records, outcome, item_err, n,
+  hipLaunchKernelGGL(k_timers_note, dim3(blocks_for(n)), dim3(256), 0, st, t, kind, records, outcome, item_err, n,
                      gp, now);
 }
 
 void launch_clock_round(const Dev &s, const TimerDev &t, int32_t now, uint32_t flags, uint8_t *cand,
                         int32_t *lpeer, int32_t *tg, int32_t *eflags, hipStream_t st) {
-  const dim3 gr(blocks256((int64_t)s.G * 8)), bl(256);
-  switch (s.P) {
-#define MRAFT_CK_CASE(PP) \
-  case PP: hipLaunchKernelGGL(k_clock_round<PP>, gr, bl, 0, st, s, t, now, flags, cand, lpeer, tg, eflags); break;
-    MRAFT_CK_CASE(1) MRAFT_CK_CASE(2) MRAFT_CK_CASE(3) MRAFT_CK_CASE(4)
-    MRAFT_CK_CASE(5) MRAFT_CK_CASE(6) MRAFT_CK_CASE(7) MRAFT_CK_CASE(8)
-#undef MRAFT_CK_CASE
-    default: break;
-  }
+  const dim3 gr(blocks_for((int64_t)s.G * 8)), bl(256);
+  with_peers<1>(s.P, [&](auto pc) {
+    hipLaunchKernelGGL(k_clock_round<decltype(pc)::value>, gr, bl, 0, st, s, t, now, flags, cand, lpeer, tg, eflags);
+  });
 }
 
 void launch_clock_resets(const Dev &s, const TimerDev &t, int32_t now, const int32_t *gflags,
                          const int32_t *lpeer, const int32_t *tg, hipStream_t st) {
-  hipLaunchKernelGGL(k_clock_resets, dim3(blocks256((int64_t)s.G * 8)), dim3(256), 0, st, s, t, now, gflags, lpeer,
+  hipLaunchKernelGGL(k_clock_resets, dim3(blocks_for((int64_t)s.G * 8)), dim3(256), 0, st, s, t, now, gflags, lpeer,
                      tg);
 }
 

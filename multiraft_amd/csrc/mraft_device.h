@@ -1,16 +1,18 @@
 // mraft_device.h — device-side building blocks shared by the gfx950 kernels.
 //
-// Wave-cooperative primitives (64-lane wavefronts, 64-bit ballots) used by the
-// AppendEntries follower path and the leader's commit scan:
-//  * wave_conflict_scan — the ConflictIndex backward scan of
-//    raft_append_entry.go:136-142, 256 terms per iteration (4 coalesced
-//    dword loads per lane in flight), first mismatch by ballot + find-first-set;
-//  * wave_merge_compare — the entry merge of :149-155: compares the entries'
-//    terms with the follower's log 256 at a time, first mismatch by ballot;
-//  * wave_copy — truncate-and-append (raft_log.go:62-75) as a streaming copy
-//    of the leader's tail into the follower's log;
-//  * wave_commit_scan — the term gate of advanceCommitIndexForLeader
-//    (:89-105): highest index in a range whose term equals currentTerm.
+// The replica state every kernel takes (Dev), the log ring (ring, term_at),
+// mark_persist, and the 64-lane wave's helpers (lane_id, first_lane, uni,
+// wave_sum), then its wave-cooperative primitives over a ring row:
+//  * wave_scan_down_ne / wave_scan_down_eq — the highest Index of a range
+//    whose term differs from / equals a value, 256 terms per iteration (4
+//    coalesced dword loads per lane in flight), found by ballot + find-first-set
+//    (the ConflictIndex scan; the term gate of advanceCommitIndexForLeader,
+//    raft_append_entry.go:89-105);
+//  * wave_conflict_scan — the ConflictIndex backward scan of :136-142;
+//  * wave_copy — a streaming copy into a replica's log (restore);
+//  * wave_copy_from_ring — a ring row unrolled into a flat buffer
+//    (persistence read-out, staged entries);
+//  * wave_terms_sorted — whether a row's terms never decrease.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,6 +57,9 @@ __device__ __forceinline__ void mark_persist(const Dev &s, int64_t slot, int bit
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 __device__ __forceinline__ int first_lane(unsigned long long m) { return __ffsll((long long)m) - 1; }
+
+// A value every lane of the wave holds alike, in an SGPR.
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Largest idx in [lo, hi] with term(idx) != a, scanning downward, in a ring
 // row whose Index `base` (the dummy) sits at `head` (row length L); returns
@@ -124,30 +129,6 @@ __device__ __forceinline__ int wave_conflict_scan(const int32_t *__restrict__ fr
   return r < lo ? fdummy + 1 : r;
 }
 
-// First k in [0, kc) with E[k] != F[k]; -1 if none.
-__device__ __forceinline__ int wave_merge_compare(const int32_t *__restrict__ E,
-                                                  const int32_t *__restrict__ F, int kc) {
-  const int lane = lane_id();
-  for (int base = 0; base < kc; base += kChunk) {
-    int e[kUnroll], f[kUnroll];
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      const int k = base + lane + kWave * u, kk = min(k, kc - 1);
-      const int x = E[kk], y = F[kk];
-      e[u] = k < kc ? x : 0;
-      f[u] = k < kc ? y : 0;
-    }
-    int r = -1;
-#pragma unroll
-    for (int u = kUnroll - 1; u >= 0; --u) {
-      const unsigned long long m = __ballot(e[u] != f[u]);
-      r = m ? base + kWave * u + first_lane(m) : r;
-    }
-    if (r >= 0) return r;
-  }
-  return -1;
-}
-
 // F[k] = E[k] for k in [0, cnt).
 __device__ __forceinline__ void wave_copy(const int32_t *__restrict__ E, int32_t *__restrict__ F,
                                           int cnt) {
@@ -201,8 +182,6 @@ __device__ __forceinline__ bool wave_terms_sorted(const int32_t *__restrict__ ro
   }
   return true;
 }
-
-__device__ __forceinline__ int shfl_i(int v, int src) { return __shfl(v, src, 64); }
 
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

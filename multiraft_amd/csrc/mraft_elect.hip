@@ -99,15 +99,10 @@ __global__ __launch_bounds__(256) void k_election_rounds(Dev s, const uint8_t *_
 
 void launch_election_rounds(const Dev &s, const uint8_t *cand, int R, int32_t *gflags,
                             hipStream_t st) {
-  const dim3 gr((unsigned)(((long long)s.G * 8 + 255) / 256)), bl(256);
-  switch (s.P) {
-#define MRAFT_EL_CASE(PP) \
-  case PP: hipLaunchKernelGGL(k_election_rounds<PP>, gr, bl, 0, st, s, cand, R, gflags); break;
-    MRAFT_EL_CASE(1) MRAFT_EL_CASE(2) MRAFT_EL_CASE(3) MRAFT_EL_CASE(4)
-    MRAFT_EL_CASE(5) MRAFT_EL_CASE(6) MRAFT_EL_CASE(7) MRAFT_EL_CASE(8)
-#undef MRAFT_EL_CASE
-    default: break;
-  }
+  const dim3 gr((unsigned)blocks_for((int64_t)s.G * 8)), bl(256);
+  with_peers<1>(s.P, [&](auto pc) {
+    hipLaunchKernelGGL(k_election_rounds<decltype(pc)::value>, gr, bl, 0, st, s, cand, R, gflags);
+  });
 }
 
 }  // namespace mraft

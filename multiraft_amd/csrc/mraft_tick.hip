@@ -78,8 +78,6 @@ __device__ __forceinline__ long long interval_len(long long a, long long b) {
   return b >= a ? b - a + 1 : 0;
 }
 
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
 // The state pointers again, read afresh from the kernel-argument segment (the
 // tick's first argument is the Dev struct). Phase C/D use this copy, so the
 // entry copy of the ~14 array pointers dies after the header instead of being
@@ -599,20 +597,11 @@ void launch_tick_p(const Dev &s, const int32_t *lpeer, int32_t *gflags, unsigned
 template <bool COUNT>
 void launch_tick_c(const Dev &s, const int32_t *lpeer, int32_t *gflags, unsigned long long *counts,
                    Export ex, hipStream_t st) {
-  switch (s.P) {
-    case 2: launch_tick_p<2, COUNT>(s, lpeer, gflags, counts, ex, st); break;
-    case 3: launch_tick_p<3, COUNT>(s, lpeer, gflags, counts, ex, st); break;
-    case 4: launch_tick_p<4, COUNT>(s, lpeer, gflags, counts, ex, st); break;
-    case 5: launch_tick_p<5, COUNT>(s, lpeer, gflags, counts, ex, st); break;
-    case 6: launch_tick_p<6, COUNT>(s, lpeer, gflags, counts, ex, st); break;
-    case 7: launch_tick_p<7, COUNT>(s, lpeer, gflags, counts, ex, st); break;
-    case 8: launch_tick_p<8, COUNT>(s, lpeer, gflags, counts, ex, st); break;
-    default: {
-      const int blocks = (s.G + 255) / 256;
-      hipLaunchKernelGGL(k_tick_p1, dim3(blocks), dim3(256), 0, st, s, lpeer, gflags, counts,
-                         COUNT ? 1 : 0, ex);
-    }
-  }
+  if (!with_peers<2>(s.P, [&](auto pc) {
+        launch_tick_p<decltype(pc)::value, COUNT>(s, lpeer, gflags, counts, ex, st);
+      }))
+    hipLaunchKernelGGL(k_tick_p1, dim3(blocks_for(s.G)), dim3(256), 0, st, s, lpeer, gflags, counts, COUNT ? 1 : 0,
+                       ex);
 }
 
 }  // namespace
@@ -633,17 +622,11 @@ void launch_replicate_tick(const Dev &s, const int32_t *lpeer, int32_t *gflags, 
 void launch_replicate_tick_light(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
                                  int32_t *exp_term_leader, const LiteBufs &lb, const StartIO *sio, hipStream_t st) {
   const Export ex{exp_commit, exp_term_leader};
-  switch (s.P) {
-    case 2: launch_tick_light_p<2>(s, lpeer, gflags, ex, lb, sio, st); break;
-    case 3: launch_tick_light_p<3>(s, lpeer, gflags, ex, lb, sio, st); break;
-    case 4: launch_tick_light_p<4>(s, lpeer, gflags, ex, lb, sio, st); break;
-    case 5: launch_tick_light_p<5>(s, lpeer, gflags, ex, lb, sio, st); break;
-    case 6: launch_tick_light_p<6>(s, lpeer, gflags, ex, lb, sio, st); break;
-    case 7: launch_tick_light_p<7>(s, lpeer, gflags, ex, lb, sio, st); break;
-    case 8: launch_tick_light_p<8>(s, lpeer, gflags, ex, lb, sio, st); break;
-    default:  // P == 1: k_tick_p1 is a lane per group already
-      if (sio) launch_start_groups(s, lpeer, *sio, st);
-      launch_tick_c<false>(s, lpeer, gflags, nullptr, ex, st);
+  if (!with_peers<2>(s.P, [&](auto pc) {
+        launch_tick_light_p<decltype(pc)::value>(s, lpeer, gflags, ex, lb, sio, st);
+      })) {  // P == 1: k_tick_p1 is a lane per group already
+    if (sio) launch_start_groups(s, lpeer, *sio, st);
+    launch_tick_c<false>(s, lpeer, gflags, nullptr, ex, st);
   }
 }
 

@@ -7,7 +7,7 @@ the oracle, bit for bit; a child process runs this file on the small-grid
 library, multiraft_amd/libmraft_hip_grid1.so).
 
 The fold is three launches (k_claim_zero, k_fold, k_fold_tail in
-multiraft_amd/csrc/mraft_kernels.hip): segments of at most GW = 8 replies fold
+multiraft_amd/csrc/mraft_fold.hip): segments of at most GW = 8 replies fold
 eight per wave on lane groups (the "group" path), longer ones one per wave in
 batches of 64 replies through a device list (the "long" path); every a1
 evaluation is a range (lo, hi) = (H + 1, top) of Indexes whose top word is

@@ -3,6 +3,7 @@
 # sources, different compile-time knobs); tools/ab_tick_pmc.sh and tools/ab_message_path.py time them.
 # Each argument is  tag[@SRCDIR]=DEFINES  e.g.  "w6=-DMRAFT_TICK_MINW=6 -DMRAFT_TICK_CMP_EPL=2"
 # or "head@/tmp/head/multiraft_amd/csrc=" (another source tree, e.g. git archive HEAD).
+# The sources and flags are the Makefile's (of the tree being built).
 # TICK_ONLY=1: recompile only mraft_tick.hip per variant (the rest from build/).
 set -e
 cd "$(dirname "$0")/../multiraft_amd/csrc"
@@ -17,24 +18,12 @@ build_one() {
   defs=${spec#*=}
   case "$tag" in *@*) cd "${tag#*@}"; tag=${tag%%@*};; esac
   mkdir -p build_$tag
-  srcs="mraft_abi mraft_kernels mraft_tick mraft_elect"
   if [ -n "$TICK_ONLY" ] && [ "$(pwd)" = "$HERE" ]; then
     # only the tick differs: the other objects come from the in-tree build
-    srcs="mraft_tick"
-    for f in mraft_abi mraft_kernels mraft_elect; do cp build/$f.o build_$tag/; done
+    cp build/mraft_*.o build_$tag/ && rm -f build_$tag/mraft_tick.o
   fi
-  for f in $srcs; do
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -mcode-object-version=5 \
-      $defs -c $f.hip -o build_$tag/$f.o 2>/dev/null &
-  done
-  g++ -O3 -std=c++17 -fPIC -c mraft_persist.cpp -o build_$tag/mraft_persist.o &
-  g++ -O3 -std=c++17 -fPIC -c mraft_router.cpp -o build_$tag/mraft_router.o &
-  wait
-  for f in mraft_abi mraft_kernels mraft_tick mraft_elect mraft_persist mraft_router; do
-    [ -f build_$tag/$f.o ] || { echo "variant $tag: $f did not compile" >&2; rm -rf build_$tag; return 1; }
-  done
-  /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT"/libmraft_hip_$tag.so build_$tag/*.o \
-    -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined || return 1
+  make -s -j16 BUILD=build_$tag DEFS="$defs" LIB="$OUT/libmraft_hip_$tag.so" LINK_EXTRA=-Wl,--no-undefined \
+    "$OUT/libmraft_hip_$tag.so" 2>/dev/null || { echo "variant $tag did not build" >&2; rm -rf build_$tag; return 1; }
   rm -rf build_$tag
   printf "%s " "$tag"; /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -mcode-object-version=5 \
       $defs -Rpass-analysis=kernel-resource-usage -c mraft_tick.hip -o /dev/null 2>&1 | \
