@@ -13,7 +13,7 @@ namespace {
 
 // The main launch's deferred list and stage offsets are counted per stripe
 // (the workgroup's XCD, blockIdx % 8), each counter on its own 128-B line of
-// the counter buffer (mraft_abi.hip ae_total, kAeTotalWords u64): one
+// the counter buffer (mraft_engine.h ae_total, kAeTotalWords u64): one
 // same-address counter took an atomic round trip per deferred item and per
 // staged item, serialised — 1.3 ms of a 2-cycle-heavy batch (r6_l7). Stripe x
 // lists its items at defer[x * n ...] and stages at stage[x * cap / 8 ...].
@@ -889,7 +889,7 @@ __global__ __launch_bounds__(64, MRAFT_AE_DMINW) void k_handle_deferred(HsArgs k
     __hip_atomic_store(ka.hint, (long long)nd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // a batch whose staged words exceed the stage: the need, for the host's
-  // next call (the stage grows to it under MRAFT_STAGE_AUTO, mraft_abi.hip)
+  // next call (the stage grows to it under MRAFT_STAGE_AUTO, mraft_abi_msg.hip)
   if (blockIdx.x == 0 && threadIdx.x == 0 && ka.hint && smax > cap8)
     __hip_atomic_store(ka.hint + 1, staged, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (nd == 0) return;

@@ -1,5 +1,5 @@
 // mraft_internal.h — the host side of the launches: the launchers each kernel
-// translation unit defines for the C-ABI implementation (mraft_abi.hip), under
+// translation unit defines for the C-ABI implementation (mraft_abi_*.hip), under
 // the name of the file that defines them, and the helpers those launchers share.
 #pragma once
 #include <hip/hip_runtime.h>

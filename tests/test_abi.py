@@ -50,6 +50,39 @@ def test_create_rejects_bad_dims_without_gpu():
     assert b"bad dims" in lib.mraft_last_error_string()
 
 
+def test_null_handle_is_rejected_without_gpu():
+    """A null handle returns before any HIP call: MRAFT_E_INVAL with "null
+    engine handle" from the entry points that need only a handle, and NULL, 0
+    or -1 from the getters."""
+    lib = _abi.lib()
+    buf = (ctypes.c_int32 * 4)()
+    soa, comm = _abi.MraftSoa(), ctypes.c_void_p()
+    calls = {
+        "mraft_set_stream": (None,),
+        "mraft_synchronize": (),
+        "mraft_allgather_status": (buf, buf, buf, _abi.HOST, 0),
+        "mraft_fanin_synchronize": (),
+        "mraft_fanin_reserve_cus": (8,),
+        "mraft_set_tick_shards": (2,),
+        "mraft_set_tick_mode": (0,),
+        "mraft_bind_state": (ctypes.byref(soa),),
+        "mraft_dims": (buf, buf, buf),
+        "mraft_comm_init": (1, 0, buf, ctypes.byref(comm)),
+    }
+    for name, args in calls.items():
+        lib.mraft_create(0, 5, 16, 0, 0, ctypes.byref(ctypes.c_void_p()))  # another error text first
+        assert getattr(lib, name)(None, *args) == _abi.E_INVAL, name
+        assert lib.mraft_last_error_string() == b"null engine handle", name
+    assert lib.mraft_get_stream(None) is None
+    assert lib.mraft_last_error_string() == b"null engine handle"
+    assert lib.mraft_fanin_stream(None) is None
+    assert lib.mraft_shard_stream(None, 0) is None
+    assert lib.mraft_get_tick_shards(None) == 0
+    assert lib.mraft_get_tick_mode(None) == -1
+    assert lib.mraft_get_stage_capacity(None) == -1
+    assert lib.mraft_tick_light_fallbacks(None) == -1
+
+
 def test_persistent_codec_round_trip_host_only():
     """mraft_encode_persistent / mraft_decode_persistent are host code: they
     run without a GPU. Round trip, exact size, and malformed-buffer rejection."""
