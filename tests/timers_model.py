@@ -4,10 +4,11 @@ step, built on the CPU oracle (oracle_lib.Oracle) and on nothing of the
 engine's timer code. Test infrastructure only.
 
 The clock step's election round is composed from the oracle's message-level
-calls (start_election for the candidates in peer order, handle_request_vote
-candidate rank by candidate rank — distinct voter slots per call — then
-process_vote_replies in voter order), which yields the per-voter grants the
-timers need; the model asserts that this composition equals
+calls (compose_round: start_election for the candidates in peer order,
+handle_request_vote candidate rank by candidate rank — distinct voter slots
+per call — then process_vote_replies in voter order; the composition takes any
+object with those three methods, so the GPU tests run it on an Engine too),
+which yields the per-voter grants the timers need; the model asserts that this composition equals
 Oracle.election_rounds on a copy of the state. The tick is Oracle.replicate_tick.
 """
 from __future__ import annotations
@@ -44,6 +45,75 @@ def draw(seed, slot, now, lo, hi):
     h = fmix((slot * 0x9E3779B9 + np.uint64(now)) & 0xFFFFFFFF)
     h = fmix(h ^ np.uint64(seed & 0xFFFFFFFF))
     return (lo + (h % np.uint64(hi - lo))).astype(np.int64)
+
+
+def deliver_round(node, G, P, cslots):
+    """The first two legs of one election round on `node` (any object with
+    start_election and handle_request_vote: the Oracle, an Engine):
+    start_election for the candidates `cslots` (ascending slots), then one
+    handle_request_vote call per candidate rank within its group (distinct
+    voter slots per call). Returns (items, seg, granted): the RV_RESULT records
+    in voter order within each candidate with their segment bounds for
+    process_vote_replies (None when P < 2 or nobody timed out), and
+    granted[G*P], the voters that granted another replica's RequestVote."""
+    granted = np.zeros(G * P, bool)
+    if not len(cslots):
+        return None, None, granted
+    args, err = node.start_election(cslots)
+    assert not err.any()
+    if P < 2:
+        return None, None, granted
+    grp = cslots // P
+    rank = np.arange(len(cslots)) - np.searchsorted(grp, grp)  # rank within its group
+    res = np.zeros((len(cslots), P), dtype=RV_RESULT)
+    for k in range(int(rank.max()) + 1):
+        idx = np.nonzero(rank == k)[0]
+        c = cslots[idx]
+        voters = np.arange(P)[None, :].repeat(len(idx), 0)
+        keep = voters != (c % P)[:, None]
+        vs = ((c // P)[:, None] * P + voters)[keep]
+        a = np.zeros(len(vs), dtype=RV_ARGS)
+        src = np.repeat(idx, P - 1)
+        a["slot"] = vs
+        a["candidate_id"] = cslots[src] % P
+        for f in ("term", "last_log_index", "last_log_term"):
+            a[f] = args[f][src]
+        rep, herr = node.handle_request_vote(a)
+        assert not herr.any()
+        granted[vs[rep["vote_granted"] != 0]] = True
+        r = res[src, vs % P]
+        r["slot"], r["peer"] = cslots[src], vs % P
+        r["args_term"], r["reply_term"], r["vote_granted"] = a["term"], rep["term"], rep["vote_granted"]
+        res[src, vs % P] = r
+    keep = np.arange(P)[None, :] != (cslots % P)[:, None]
+    items = res[keep]                                  # voter order within each candidate
+    seg = np.arange(len(cslots) + 1, dtype=np.int64) * (P - 1)
+    return items, seg, granted
+
+
+def tally_round(node, G, P, items, seg):
+    """The third leg: one process_vote_replies call over deliver_round's
+    records. Returns (group flags, became[G*P], the per-item flags)."""
+    became = np.zeros(G * P, bool)
+    gf = np.zeros(G, np.int32)
+    if items is None:
+        return gf, became, np.zeros(0, np.int32)
+    fl, terr = node.process_vote_replies(items, seg)
+    assert not terr.any()
+    lead = (fl & _abi.F_BECAME_LEADER) != 0
+    became[items["slot"][lead]] = True
+    np.bitwise_or.at(gf, items["slot"][lead] // P, _abi.G_ELECTED)
+    sd = (fl & _abi.F_STEPPED_DOWN) != 0
+    np.bitwise_or.at(gf, items["slot"][sd] // P, _abi.G_STEPPED_DOWN)
+    return gf, became, fl
+
+
+def compose_round(node, G, P, cslots):
+    """One election round from the message-level calls on `node`:
+    (group flags, granted[G*P], became[G*P])."""
+    items, seg, granted = deliver_round(node, G, P, cslots)
+    gf, became, _ = tally_round(node, G, P, items, seg)
+    return gf, granted, became
 
 
 class TimersModel:
@@ -133,48 +203,7 @@ class TimersModel:
         G, P, o = self.G, self.P, self.o
         check = Oracle(G, P, self.L, o.st)
         check.st["terms_sorted"][:] = o.st["terms_sorted"]
-        cslots = np.nonzero(cand)[0].astype(np.int32)
-        granted = np.zeros(G * P, bool)
-        became = np.zeros(G * P, bool)
-        gf = np.zeros(G, np.int32)
-        if len(cslots):
-            args, err = o.start_election(cslots)
-            assert not err.any()
-            grp = cslots // P
-            rank = np.arange(len(cslots)) - np.searchsorted(grp, grp)  # rank within its group
-            res = np.zeros((len(cslots), P), dtype=RV_RESULT)
-            for k in range(int(rank.max()) + 1):
-                idx = np.nonzero(rank == k)[0]
-                if P < 2:
-                    break
-                c = cslots[idx]
-                voters = np.arange(P)[None, :].repeat(len(idx), 0)
-                keep = voters != (c % P)[:, None]
-                vs = ((c // P)[:, None] * P + voters)[keep]
-                a = np.zeros(len(vs), dtype=RV_ARGS)
-                src = np.repeat(idx, P - 1)
-                a["slot"] = vs
-                a["candidate_id"] = cslots[src] % P
-                for f in ("term", "last_log_index", "last_log_term"):
-                    a[f] = args[f][src]
-                rep, herr = o.handle_request_vote(a)
-                assert not herr.any()
-                granted[vs[rep["vote_granted"] != 0]] = True
-                r = res[src, vs % P]
-                r["slot"], r["peer"] = cslots[src], vs % P
-                r["args_term"], r["reply_term"], r["vote_granted"] = a["term"], rep["term"], rep["vote_granted"]
-                res[src, vs % P] = r
-            if P >= 2:
-                keep = np.arange(P)[None, :] != (cslots % P)[:, None]
-                items = res[keep]                                  # voter order within each candidate
-                seg = np.arange(len(cslots) + 1, dtype=np.int64) * (P - 1)
-                fl, terr = o.process_vote_replies(items, seg)
-                assert not terr.any()
-                lead = (fl & _abi.F_BECAME_LEADER) != 0
-                became[items["slot"][lead]] = True
-                np.bitwise_or.at(gf, items["slot"][lead] // P, _abi.G_ELECTED)
-                sd = (fl & _abi.F_STEPPED_DOWN) != 0
-                np.bitwise_or.at(gf, items["slot"][sd] // P, _abi.G_STEPPED_DOWN)
+        gf, granted, became = compose_round(o, G, P, np.nonzero(cand)[0].astype(np.int32))
         # the composition is the storm's round
         bits = (cand.reshape(G, P).astype(np.int64) << np.arange(P)).sum(axis=1).astype(np.uint8)
         cgf = check.election_rounds(bits[None, :])
