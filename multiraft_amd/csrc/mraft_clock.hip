@@ -50,104 +50,47 @@ __global__ __launch_bounds__(256) void k_timers_arm(TimerDev t, const int32_t *_
 }
 
 // ---------------------------------------------------------------- ticker
-// ticker() for every slot, the two lists compacted in ascending slot order in
-// three launches (per-block counts, one-workgroup exclusive scan per list,
-// emit), as the compacted applier does (mraft_kernels.hip).
-struct TickerLane {
-  bool edue, hdue, leader;
-};
-
-__device__ __forceinline__ TickerLane ticker_lane(const Dev &s, const TimerDev &t, int64_t i, int64_t gp,
-                                                  int now) {
-  TickerLane l{false, false, false};
+// ticker() for every slot, its two lists compacted in ascending slot order
+// (mraft_device.h "ordered compaction": list 0 the election timeouts of
+// non-leaders, raft.go:112-114, list 1 the leaders' heartbeats, :119-121).
+struct TickerLane { bool edue, hdue, list[2]; };
+__device__ __forceinline__ TickerLane ticker_lane(const Dev &s, const TimerDev &t, int64_t i, int64_t gp, int now) {
+  TickerLane l{false, false, {false, false}};
   if (i < gp) {
+    const bool leader = s.role[i] == kLeader;
     l.edue = t.ed[i] <= now;
     l.hdue = t.hd[i] <= now;
-    l.leader = s.role[i] == kLeader;
+    l.list[0] = l.edue && !leader;
+    l.list[1] = l.hdue && leader;
   }
   return l;
 }
 
-__global__ __launch_bounds__(256) void k_ticker_count(Dev s, TimerDev t, int now, int32_t *__restrict__ bcnt,
-                                                      int64_t nb) {
-  const int64_t gp = (int64_t)s.G * s.P;
+__global__ __launch_bounds__(kCompactBlock) void k_ticker_count(Dev s, TimerDev t, int now,
+                                                                int32_t *__restrict__ bcnt) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const TickerLane l = ticker_lane(s, t, i, gp, now);
-  const unsigned long long me = __ballot(l.edue && !l.leader);          // raft.go:112-114
-  const unsigned long long mh = __ballot(l.hdue && l.leader);           // :119-121
-  __shared__ int wc[2][4];
-  if (lane_id() == 0) {
-    wc[0][threadIdx.x >> 6] = __popcll(me);
-    wc[1][threadIdx.x >> 6] = __popcll(mh);
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const int k = threadIdx.x;
-    bcnt[k * nb + blockIdx.x] = wc[k][0] + wc[k][1] + wc[k][2] + wc[k][3];
-  }
+  const TickerLane l = ticker_lane(s, t, i, (int64_t)s.G * s.P, now);
+  compact_count<2>(l.list, bcnt, gridDim.x);
 }
 
-// Workgroup k scans list k's block counts in place (exclusive), 1,024 at a
-// time with a carry, and writes the list's total.
-__global__ __launch_bounds__(1024) void k_ticker_scan(int32_t *__restrict__ bcnt, int64_t nb,
-                                                      int64_t *__restrict__ total_e,
-                                                      int64_t *__restrict__ total_h) {
-  __shared__ int64_t part[1024];
-  int32_t *c = bcnt + blockIdx.x * nb;
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nb; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t v = i < nb ? c[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {  // inclusive Hillis-Steele scan
-      const int64_t add = threadIdx.x >= (unsigned)o ? part[threadIdx.x - o] : 0;
-      __syncthreads();
-      part[threadIdx.x] += add;
-      __syncthreads();
-    }
-    if (i < nb) c[i] = (int32_t)(carry + part[threadIdx.x] - v);
-    const int64_t chunk = part[1023];
-    __syncthreads();
-    carry += chunk;
-  }
-  if (threadIdx.x == 0) *(blockIdx.x == 0 ? total_e : total_h) = carry;
-}
-
-__global__ __launch_bounds__(256) void k_ticker_emit(Dev s, TimerDev t, int now, const int32_t *__restrict__ boff,
-                                                     int64_t nb, int64_t cap_e, int64_t cap_h,
-                                                     int32_t *__restrict__ oe, int32_t *__restrict__ oh) {
-  const int64_t gp = (int64_t)s.G * s.P;
+__global__ __launch_bounds__(kCompactBlock) void k_ticker_emit(
+    Dev s, TimerDev t, int now, const int32_t *__restrict__ boff, int64_t cap_e, int64_t cap_h,
+    int32_t *__restrict__ oe, int32_t *__restrict__ oh) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const TickerLane l = ticker_lane(s, t, i, gp, now);
-  const bool le = l.edue && !l.leader, lh = l.hdue && l.leader;
-  const unsigned long long me = __ballot(le), mh = __ballot(lh);
-  __shared__ int wc[2][4];
-  if (lane_id() == 0) {
-    wc[0][threadIdx.x >> 6] = __popcll(me);
-    wc[1][threadIdx.x >> 6] = __popcll(mh);
-  }
-  __syncthreads();
-  const int w = threadIdx.x >> 6;
-  int64_t offe = boff[blockIdx.x], offh = boff[nb + blockIdx.x];
-  for (int k = 0; k < w; ++k) {
-    offe += wc[0][k];
-    offh += wc[1][k];
-  }
-  const unsigned long long below = (1ull << lane_id()) - 1;
-  offe += __popcll(me & below);
-  offh += __popcll(mh & below);
+  const TickerLane l = ticker_lane(s, t, i, (int64_t)s.G * s.P, now);
+  int64_t off[2];
+  compact_offsets<2>(l.list, boff, gridDim.x, off);
   // A listed slot whose entry does not fit keeps its due timer (the caller
   // calls again for the rest); every other due timer is reset (:111, :118).
   if (l.edue) {
-    const bool fits = offe < cap_e;
-    if (le && fits) oe[offe] = (int32_t)i;
-    if (!le || fits) t.ed[i] = election_deadline(t, i, now);
+    const bool fits = off[0] < cap_e;
+    if (l.list[0] && fits) oe[off[0]] = (int32_t)i;
+    if (!l.list[0] || fits) t.ed[i] = election_deadline(t, i, now);
   }
   if (l.hdue) {
-    const bool fits = offh < cap_h;
-    if (lh && fits) oh[offh] = (int32_t)i;
-    if (!lh || fits) t.hd[i] = heartbeat_deadline(t, now);
+    const bool fits = off[1] < cap_h;
+    if (l.list[1] && fits) oh[off[1]] = (int32_t)i;
+    if (!l.list[1] || fits) t.hd[i] = heartbeat_deadline(t, now);
   }
 }
 
@@ -330,10 +273,10 @@ void launch_timers_arm(const TimerDev &t, const int32_t *slots, int64_t n, int64
 void launch_ticker(const Dev &s, const TimerDev &t, int32_t now, int32_t *bcnt, int32_t *oe, int64_t cap_e,
                    int64_t *n_e, int32_t *oh, int64_t cap_h, int64_t *n_h, hipStream_t st) {
   const int64_t nb = ticker_blocks((int64_t)s.G * s.P);
-  hipLaunchKernelGGL(k_ticker_count, dim3((unsigned)nb), dim3(256), 0, st, s, t, now, bcnt, nb);
-  hipLaunchKernelGGL(k_ticker_scan, dim3(2), dim3(1024), 0, st, bcnt, nb, n_e, n_h);
-  hipLaunchKernelGGL(k_ticker_emit, dim3((unsigned)nb), dim3(256), 0, st, s, t, now, bcnt, nb, cap_e, cap_h, oe,
-                     oh);
+  hipLaunchKernelGGL(k_ticker_count, dim3((unsigned)nb), dim3(kCompactBlock), 0, st, s, t, now, bcnt);
+  launch_compact_scan(bcnt, nb, 2, n_e, n_h, st);
+  hipLaunchKernelGGL(k_ticker_emit, dim3((unsigned)nb), dim3(kCompactBlock), 0, st, s, t, now, bcnt, cap_e, cap_h,
+                     oe, oh);
 }
 
 void launch_timers_note(const TimerDev &t, int kind, const void *records, const void *outcome,

@@ -12,7 +12,11 @@
 //  * wave_copy — a streaming copy into a replica's log (restore);
 //  * wave_copy_from_ring — a ring row unrolled into a flat buffer
 //    (persistence read-out, staged entries);
-//  * wave_terms_sorted — whether a row's terms never decrease.
+//  * wave_terms_sorted — whether a row's terms never decrease;
+// and for whole grids xcd_contiguous (each XCD a contiguous range of the
+// workgroups) and compact_count / compact_offsets, the in-block part of an
+// ordered compaction of K lists (the compacted applier, the ticker). The
+// rules of single items (claims, Start, the Index domain) are in mraft_rules.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -188,6 +192,61 @@ __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md
+// §Workgroup dispatch). The index workgroup b of nb takes so that each XCD
+// serves one contiguous range (the first nb % 8 XCDs one workgroup more): a
+// permutation of [0, nb), for speed only.
+template <typename T>
+__device__ __forceinline__ T xcd_contiguous(T b, T nb) {
+  const T x = b & 7, per = nb >> 3, rem = nb & 7;
+  return x * per + min(x, rem) + (b >> 3);
+}
+
+// ---------------------------------------------------------------- ordered compaction
+// K lists of the items that satisfy K predicates, each in ascending item
+// order, from workgroups of kCompactBlock threads, a thread per item: a count
+// launch (compact_count), an exclusive scan of the block counts
+// (launch_compact_scan, mraft_internal.h), an emit launch (compact_offsets).
+// List k's block counts, then offsets, are bcnt[k * nb + block].
+constexpr int kCompactBlock = 256, kCompactWaves = kCompactBlock / kWave;
+
+// The wave's ballots m and, after a barrier, every wave's counts wc.
+template <int K>
+__device__ __forceinline__ void compact_ballots(const bool (&pred)[K], unsigned long long (&m)[K],
+                                                int (&wc)[K][kCompactWaves]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    m[k] = __ballot(pred[k]);
+    if (lane_id() == 0) wc[k][threadIdx.x >> 6] = __popcll(m[k]);
+  }
+  __syncthreads();
+}
+
+// Count launch, every thread: the workgroup's count of each list.
+template <int K>
+__device__ __forceinline__ void compact_count(const bool (&pred)[K], int32_t *__restrict__ bcnt, int64_t nb) {
+  __shared__ int wc[K][kCompactWaves];
+  unsigned long long m[K];
+  compact_ballots<K>(pred, m, wc);
+  const int k = threadIdx.x;
+  if (k < K) bcnt[k * nb + blockIdx.x] = wc[k][0] + wc[k][1] + wc[k][2] + wc[k][3];
+}
+
+// Emit launch, every thread: off[k] = its position in list k where pred[k]
+// holds (the scanned block offset, the waves below, the lanes below).
+template <int K>
+__device__ __forceinline__ void compact_offsets(const bool (&pred)[K], const int32_t *__restrict__ boff, int64_t nb,
+                                                int64_t (&off)[K]) {
+  __shared__ int wc[K][kCompactWaves];
+  unsigned long long m[K];
+  compact_ballots<K>(pred, m, wc);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    off[k] = boff[k * nb + blockIdx.x] + __popcll(m[k] & ((1ull << lane_id()) - 1));
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off[k] += wc[k][w];
+  }
 }
 
 }  // namespace mraft

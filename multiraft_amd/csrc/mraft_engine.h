@@ -337,8 +337,7 @@ template <>
 constexpr int slot_offset<int32_t>() { return 0; }
 template <class Rec>
 void claim(mraft_engine *h, const Rec *items, int64_t n, const int64_t *seg_begin, int32_t *err) {
-  launch_claim(items, n, sizeof(Rec), slot_offset<Rec>(), seg_begin, gp_of(h), h->P, h->claim, h->epoch, err,
-               h->stream);
+  launch_claim(items, n, sizeof(Rec), slot_offset<Rec>(), seg_begin, gp_of(h), h->claim, h->epoch, err, h->stream);
 }
 
 // What the three reply folds share (mraft_process_*_replies): the argument
@@ -378,13 +377,13 @@ int fold_replies(mraft_engine *h, const Rec *items, int64_t n, const int64_t *se
 template <class Rec>
 int fold_records(mraft_engine *h, const Rec *items, int64_t n, const int64_t *seg_begin, int64_t n_seg,
                  int32_t *out_flags, int32_t *item_err, int32_t where,
-                 void (*fold)(const Dev &, const Rec *, int64_t, const int64_t *, int64_t, int32_t *, int32_t *,
-                              int32_t *, hipStream_t)) {
+                 void (*fold)(const Dev &, const Rec *, const int64_t *, int64_t, int32_t *, int32_t *, int32_t *,
+                              hipStream_t)) {
   return fold_replies(h, items, n, seg_begin, n_seg, out_flags, item_err, where, [=](const FoldBufs<Rec> &b) -> int {
     HIP_TRY(hipMemsetAsync(b.fl, 0, sizeof(int32_t) * n, h->stream));
     HIP_TRY(hipMemsetAsync(b.e, 0, sizeof(int32_t) * n, h->stream));
     claim(h, b.it, b.ns, b.sb, b.se);
-    fold(dev_of(h), b.it, n, b.sb, b.ns, b.se, b.fl, b.e, h->stream);
+    fold(dev_of(h), b.it, b.sb, b.ns, b.se, b.fl, b.e, h->stream);
     return MRAFT_OK;
   });
 }

@@ -5,6 +5,7 @@
 // (k_fold_tail).
 #include "mraft_device.h"
 #include "mraft_internal.h"
+#include "mraft_rules.h"
 
 namespace mraft {
 
@@ -36,16 +37,7 @@ __global__ void k_claim_zero(const char *__restrict__ items, int64_t n, int stri
   }
   if (i == 0 && zc) *zc = 0;  // no a1 range pending for k_fold_tail's scans yet
   if (i == 0 && zl) *zl = 0;  // no long segment for k_fold_tail yet
-  if (i >= n) return;
-  int64_t rec = i;
-  if (seg_begin) {
-    if (seg_begin[i] >= seg_begin[i + 1]) { err[i] = 0; return; }
-    rec = seg_begin[i];
-  }
-  const int32_t slot = *(const int32_t *)(items + rec * stride + slot_off);
-  if (slot < 0 || slot >= gp) { err[i] = MRAFT_ITEM_BAD_SLOT; return; }
-  err[i] = 0;
-  atomicMax(&claim[slot], ((unsigned long long)epoch << 32) | (0xFFFFFFFFull - (uint64_t)i));
+  if (i < n) claim_item(items, i, stride, slot_off, seg_begin, gp, claim, epoch, err);
 }
 
 // ---------------------------------------------------------------- a2 + a1
@@ -54,7 +46,7 @@ __global__ void k_claim_zero(const char *__restrict__ items, int64_t n, int stri
 // nextIndex stay int32); else the segment is malformed, as in the oracle
 // (reply_index_ok).
 __device__ __forceinline__ bool reply_index_ok(int prev, int n) {
-  return n >= 0 && (int64_t)prev + n <= (int64_t)INT32_MAX - 1;
+  return n >= 0 && index_in_domain((int64_t)prev + n);
 }
 
 template <int P>
@@ -204,7 +196,8 @@ __device__ __forceinline__ void fold_segment(const Dev &s, const mraft_ae_result
   // segment wins (k_claim_zero's atomicMax on the inverted index), the others
   // are rejected before any state change — loaded beside the state
   const unsigned long long cw = !bad ? claim[slot] : 0ull;
-  if (!bad && __builtin_amdgcn_readfirstlane((int)(uint32_t)cw) != (int)(0xFFFFFFFFull - (uint64_t)sg) ) bad = MRAFT_ITEM_DUP_SLOT;
+  // (claim_won(cw, epoch, sg), the halves of claim_tag compared apart)
+  if (!bad && __builtin_amdgcn_readfirstlane((int)(uint32_t)cw) != (int)(uint32_t)claim_tag(epoch, sg)) bad = MRAFT_ITEM_DUP_SLOT;
   if (!bad && (uint32_t)(cw >> 32) != epoch) bad = MRAFT_ITEM_DUP_SLOT;
   int term = __builtin_amdgcn_readlane(vs, 16), role = __builtin_amdgcn_readlane(vs, 17),
       commit = __builtin_amdgcn_readlane(vs, 18);
@@ -430,7 +423,7 @@ __device__ __forceinline__ void fold_groupw(const Dev &s, const mraft_ae_result 
   }
   // a slot claimed by an earlier segment of the batch: rejected (k_fold's check)
   const unsigned long long cw = (cnt && !bad) ? claim[slot] : 0ull;
-  if (cnt && !bad && ((uint32_t)cw != (uint32_t)(0xFFFFFFFFull - (uint64_t)sg) || (uint32_t)(cw >> 32) != epoch))
+  if (cnt && !bad && ((uint32_t)cw != (uint32_t)claim_tag(epoch, sg) || (uint32_t)(cw >> 32) != epoch))
     bad = MRAFT_ITEM_DUP_SLOT;
   int term = gw_bcast<GW>(vb, 0), role = gw_bcast<GW>(vb, 1), commit = gw_bcast<GW>(vb, 2);
   const int last = gw_bcast<GW>(vb, 3), dummy = gw_bcast<GW>(vb, 4), head = gw_bcast<GW>(vb, 5);
@@ -544,6 +537,7 @@ __global__ __launch_bounds__(64, 8) void k_fold(Dev s, const mraft_ae_result *__
   if ((int64_t)gridDim.x * NG >= n_seg) {
     // each XCD a contiguous range of waves: neighbouring waves' segments
     // share the lines of the replica arrays in one L2
+    // (xcd_contiguous(b, nb) written out: the call compiles to other code here)
     const int64_t nb = gridDim.x, b = blockIdx.x, x = b & 7, per = nb >> 3, rem = nb & 7;
     const int64_t wb = x * per + min(x, rem) + (b >> 3);
     fold_groupw<P, GW>(s, items, n_items, seg_begin, NG * wb, n_seg, seg_err, claim, epoch, flags, item_err, pend,

@@ -6,6 +6,7 @@
 #include "mraft_device.h"
 #include "mraft_internal.h"
 #include "mraft_pass.h"
+#include "mraft_rules.h"
 
 namespace mraft {
 
@@ -78,11 +79,7 @@ __device__ __forceinline__ bool ae_ref_ok(const mraft_ae_args &a, int64_t n_log,
 // leave room for nextIndex = Index + 1 in int32. Outside it the item is
 // malformed (MRAFT_ITEM_BAD_SLOT), as in the oracle.
 __device__ __forceinline__ bool ae_index_ok(const mraft_ae_args &a) {
-  return (int64_t)a.prev_log_index + a.n_entries <= (int64_t)INT32_MAX - 1;
-}
-
-__device__ __forceinline__ unsigned long long claim_tag(uint32_t epoch, int64_t i) {
-  return ((unsigned long long)epoch << 32) | (0xFFFFFFFFull - (uint64_t)i);
+  return index_in_domain((int64_t)a.prev_log_index + a.n_entries);
 }
 
 __device__ __forceinline__ AeKey ae_key(const mraft_ae_args &a, int64_t gp, int64_t n_log, int L) {
@@ -402,7 +399,7 @@ __device__ __forceinline__ void handle_one(const HsArgs &k0, int64_t first, int 
     }
     if (ok) rhead = s.head[srow];
     if (MODE == HM_MAIN) {
-      dup = cs != claim_tag(k0.epoch, i);
+      dup = !claim_won(cs, k0.epoch, i);
       dfr = !dup && ok && sm == k0.epoch;                              // `written`: deferred
       stg = dfr && nn > 0 && (uint32_t)(cr >> 32) == k0.epoch;        // and `read`: staged
     }
@@ -430,8 +427,7 @@ __device__ __forceinline__ void handle_one(const HsArgs &k0, int64_t first, int 
   if (MODE == HM_MAIN && __ballot(dfr)) {
     // the claimant of the row this item reads (from the claim word loaded above),
     // for an item that reads anything (the writer check is the fallback's)
-    const int wraw = (nn > 0 && ae_index_ok(a) && (uint32_t)(cr >> 32) == k0.epoch)
-                         ? (int)(0xFFFFFFFFu - (uint32_t)cr) : -1;
+    const int wraw = (nn > 0 && ae_index_ok(a) && (uint32_t)(cr >> 32) == k0.epoch) ? claim_index(cr) : -1;
     defer_lanes(k0, dfr, stg, i, nn, s.log + srow * L, rhead, (int)(a.entries_offset % L), L, wraw);
   }
   if (k0.res && mine && cls != AE_DEFER) {
@@ -648,9 +644,9 @@ __global__ __launch_bounds__(64, MRAFT_AE_MINW) void k_handle_set(HsArgs ka) {
   const int64_t nb = MODE == HM_HOST ? ka.n : (ka.n + NI - 1) / NI;
   int64_t v = blockIdx.x;
   {
-    const int64_t x = v & 7, per = nb >> 3, rem = nb & 7, j = v >> 3;
-    if (j >= per + (x < rem ? 1 : 0)) return;
-    v = x * per + min(x, rem) + j;
+    const int64_t x = v & 7, per = nb >> 3, rem = nb & 7;
+    if ((v >> 3) >= per + (x < rem ? 1 : 0)) return;
+    v = xcd_contiguous(v, nb);
   }
   if (MODE == HM_HOST) {
     handle_one<NI, HM_HOST>(ka, v, 1);

@@ -51,14 +51,13 @@ void launch_terms_sorted(const Dev &s, hipStream_t st);  // terms_sorted recompu
 // of `stride` bytes; or, with seg_begin, the slot of segment i's first item)
 // wins iff it is the lowest index addressing its slot in this call.
 void launch_claim(const void *items, int64_t n, int stride, int slot_off, const int64_t *seg_begin,
-                  int64_t gp, int peers, unsigned long long *claim, uint32_t epoch, int32_t *err,
-                  hipStream_t st);
+                  int64_t gp, unsigned long long *claim, uint32_t epoch, int32_t *err, hipStream_t st);
 
 void launch_gather_args(const Dev &s, const int32_t *slots, const int32_t *peers, int64_t n,
                         mraft_ae_args *out, int32_t *err, hipStream_t st);
 // Start: the slot claims (k_claim) and k_start, which checks them itself.
 void launch_start(const Dev &s, const int32_t *slots, const int32_t *counts, int64_t n, int32_t *oi,
-                  int32_t *ot, int32_t *ol, int32_t *err, const unsigned long long *claim, uint32_t epoch,
+                  int32_t *ot, int32_t *ol, int32_t *err, unsigned long long *claim, uint32_t epoch,
                   hipStream_t st);
 // mraft_start_and_tick: per group, counts[g] entries to Start at replica
 // leader_peer[g] (0: none), and Start's outputs per group.
@@ -71,6 +70,11 @@ struct StartIO {
 void launch_start_groups(const Dev &s, const int32_t *lpeer, const StartIO &sio, hipStream_t st);
 void launch_collect_apply(const Dev &s, int32_t *from, int32_t *to, int32_t *snap_index, int32_t *snap_term,
                           hipStream_t st);
+// Ordered compaction (mraft_device.h): the workgroups of its count and emit
+// launches over n items, and the scan between them — workgroup k < lists <= 2
+// scans list k's nb block counts in place (exclusive) and writes total<k>.
+inline int64_t compact_blocks(int64_t n) { return (n + kCompactBlock - 1) / kCompactBlock; }
+void launch_compact_scan(int32_t *bcnt, int64_t nb, int lists, int64_t *total0, int64_t *total1, hipStream_t st);
 void launch_collect_apply_compact(const Dev &s, int32_t *scratch_bcnt, int64_t cap, int32_t *oslot,
                                   int32_t *osnap_index, int32_t *osnap_term, int32_t *ofrom, int32_t *oto,
                                   int64_t *total, hipStream_t st);
@@ -80,16 +84,14 @@ void launch_gather_is(const Dev &s, const int32_t *slots, const int32_t *peers, 
                       mraft_is_args *out, int32_t *err, hipStream_t st);
 void launch_handle_is(const Dev &s, const mraft_is_args *args, int64_t n, mraft_is_reply *rep,
                       int32_t *flags, int32_t *err, hipStream_t st);
-void launch_process_is(const Dev &s, const mraft_is_result *items, int64_t n, const int64_t *seg_begin,
-                       int64_t n_seg, int32_t *seg_err, int32_t *flags, int32_t *item_err,
-                       hipStream_t st);
+void launch_process_is(const Dev &s, const mraft_is_result *items, const int64_t *seg_begin, int64_t n_seg,
+                       int32_t *seg_err, int32_t *flags, int32_t *item_err, hipStream_t st);
 void launch_start_election(const Dev &s, const int32_t *slots, int64_t n, mraft_rv_args *out,
                            int32_t *err, hipStream_t st);
 void launch_handle_rv(const Dev &s, const mraft_rv_args *args, int64_t n, mraft_rv_reply *rep,
                       int32_t *err, hipStream_t st);
-void launch_tally(const Dev &s, const mraft_rv_result *items, int64_t n, const int64_t *seg_begin,
-                  int64_t n_seg, int32_t *seg_err, int32_t *flags, int32_t *item_err,
-                  hipStream_t st);
+void launch_tally(const Dev &s, const mraft_rv_result *items, const int64_t *seg_begin, int64_t n_seg,
+                  int32_t *seg_err, int32_t *flags, int32_t *item_err, hipStream_t st);
 void launch_collect_persist(const Dev &s, int32_t *out, hipStream_t st);
 void launch_read_persistent_hdr(const Dev &s, const int32_t *slots, int64_t n,
                                 mraft_persistent *out, hipStream_t st);
@@ -191,10 +193,10 @@ struct TimerDev {
 void launch_timers_arm_all(const TimerDev &t, int64_t gp, int32_t now, hipStream_t st);
 void launch_timers_arm(const TimerDev &t, const int32_t *slots, int64_t n, int64_t gp, int32_t now,
                        hipStream_t st);
-// mraft_ticker: count / scan / emit (as launch_collect_apply_compact). bcnt
-// holds 2 * ticker_blocks(gp) words: the election list's block counts, then
-// the heartbeat list's.
-inline int64_t ticker_blocks(int64_t gp) { return (gp + 255) / 256; }
+// mraft_ticker: an ordered compaction of two lists. bcnt holds
+// 2 * ticker_blocks(gp) words: the election list's block counts, then the
+// heartbeat list's.
+inline int64_t ticker_blocks(int64_t gp) { return compact_blocks(gp); }
 void launch_ticker(const Dev &s, const TimerDev &t, int32_t now, int32_t *bcnt, int32_t *oe, int64_t cap_e,
                    int64_t *n_e, int32_t *oh, int64_t cap_h, int64_t *n_h, hipStream_t st);
 void launch_timers_note(const TimerDev &t, int kind, const void *records, const void *outcome,

@@ -6,6 +6,7 @@
 // mraft_fold.hip, the fused co-resident tick in mraft_tick.hip.
 #include "mraft_device.h"
 #include "mraft_internal.h"
+#include "mraft_rules.h"
 
 namespace mraft {
 
@@ -29,37 +30,18 @@ __global__ void k_init_state(Dev s) {
 
 // ---------------------------------------------------------------- claims
 __global__ void k_claim(const char *__restrict__ items, int64_t n, int stride, int slot_off,
-                        const int64_t *__restrict__ seg_begin, int64_t gp, int peers,
-                        unsigned long long *__restrict__ claim, uint32_t epoch,
-                        int32_t *__restrict__ err) {
+                        const int64_t *__restrict__ seg_begin, int64_t gp, unsigned long long *__restrict__ claim,
+                        uint32_t epoch, int32_t *__restrict__ err) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int64_t rec = i;
-  if (seg_begin) {
-    if (seg_begin[i] >= seg_begin[i + 1]) { err[i] = 0; return; }
-    rec = seg_begin[i];
-  }
-  const int32_t slot = *(const int32_t *)(items + rec * stride + slot_off);
-  (void)peers;
-  if (slot < 0 || slot >= gp) { err[i] = MRAFT_ITEM_BAD_SLOT; return; }
-  err[i] = 0;
-  atomicMax(&claim[slot], ((unsigned long long)epoch << 32) | (0xFFFFFFFFull - (uint64_t)i));
+  if (i < n) claim_item(items, i, stride, slot_off, seg_begin, gp, claim, epoch, err);
 }
 
 __global__ void k_claim_check(const char *__restrict__ items, int64_t n, int stride, int slot_off,
-                              const int64_t *__restrict__ seg_begin,
-                              const unsigned long long *__restrict__ claim, uint32_t epoch,
-                              int32_t *__restrict__ err) {
+                              const int64_t *__restrict__ seg_begin, const unsigned long long *__restrict__ claim,
+                              uint32_t epoch, int32_t *__restrict__ err) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n || err[i]) return;
-  int64_t rec = i;
-  if (seg_begin) {
-    if (seg_begin[i] >= seg_begin[i + 1]) return;
-    rec = seg_begin[i];
-  }
-  const int32_t slot = *(const int32_t *)(items + rec * stride + slot_off);
-  if (claim[slot] != (((unsigned long long)epoch << 32) | (0xFFFFFFFFull - (uint64_t)i)))
-    err[i] = MRAFT_ITEM_DUP_SLOT;
+  if (claim_lost(items, i, stride, slot_off, seg_begin, claim, epoch)) err[i] = MRAFT_ITEM_DUP_SLOT;
 }
 
 // ---------------------------------------------------------------- a3
@@ -108,65 +90,38 @@ __global__ void k_gather_args(Dev s, const int32_t *__restrict__ slots,
 // ---------------------------------------------------------------- Start
 // The duplicate-slot check (k_claim_check's) is done here, on the claim word
 // k_claim left: one launch fewer per Start call.
-__global__ void k_start(Dev s, const int32_t *__restrict__ slots, const int32_t *__restrict__ counts,
-                        int64_t n, int32_t *__restrict__ oi, int32_t *__restrict__ ot,
-                        int32_t *__restrict__ ol, int32_t *__restrict__ err,
-                        const unsigned long long *__restrict__ claim, uint32_t epoch) {
+__global__ void k_start(Dev s, const int32_t *__restrict__ slots, const int32_t *__restrict__ counts, int64_t n,
+                        int32_t *__restrict__ oi, int32_t *__restrict__ ot, int32_t *__restrict__ ol,
+                        int32_t *__restrict__ err, const unsigned long long *__restrict__ claim, uint32_t epoch) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int idx = -1, term = -1, isl = 0;
+  StartOutcome o{-1, -1, 0, 0};
   if (!err[i]) {
-    const int sl = slots[i], k = counts ? counts[i] : 1;
-    if (claim[sl] != (((unsigned long long)epoch << 32) | (0xFFFFFFFFull - (uint64_t)i))) {
-      err[i] = MRAFT_ITEM_DUP_SLOT;
-    } else if (k < 1) {
-      err[i] = MRAFT_ITEM_BAD_SLOT;
-    } else if (s.role[sl] == kLeader) {                                // raft.go:93-95
-      const int last = s.last[sl], dummy = s.dummy[sl], t = s.term[sl], h = s.head[sl];
-      if ((int64_t)last + k - dummy > (int64_t)s.L - 1 || (int64_t)last + k > (int64_t)INT32_MAX - 1) {
-        err[i] = MRAFT_ITEM_LOG_FULL;
-      } else {
-        // terms_sorted: k entries of currentTerm after the last one
-        if (last > dummy && s.log[(int64_t)sl * s.L + ring(last - dummy + h, s.L)] > t) s.srt[sl] = 0;
-        for (int j = 1; j <= k; ++j) s.log[(int64_t)sl * s.L + ring(last + j - dummy + h, s.L)] = t;  // :96-100
-        s.last[sl] = last + k;
-        mark_persist(s, sl, MRAFT_PERSIST_STATE);                      // :101
-        idx = last + 1; term = t; isl = 1;                             // :103
-      }
-    }
+    const int k = counts ? counts[i] : 1;
+    if (claim_lost((const char *)slots, i, sizeof(int32_t), 0, nullptr, claim, epoch)) o.err = MRAFT_ITEM_DUP_SLOT;
+    else if (k < 1) o.err = MRAFT_ITEM_BAD_SLOT;
+    else o = start_at(s, slots[i], k);
+    if (o.err) err[i] = o.err;
   }
-  oi[i] = idx; ot[i] = term; ol[i] = isl;
+  oi[i] = o.index; ot[i] = o.term; ol[i] = o.is_leader;
 }
 
 // Start at every group's leader replica (mraft_start_and_tick on the full
-// tick's path): slot g * P + leader_peer[g], counts[g] entries (0: none), the
-// rules of k_start; a group whose leader_peer is out of range starts nothing
+// tick's path): slot g * P + leader_peer[g], counts[g] entries (0: none); a
+// group whose leader_peer is out of range starts nothing
 // (MRAFT_ITEM_BAD_SLOT when it asked for entries with leader_peer >= P).
 __global__ void k_start_groups(Dev s, const int32_t *__restrict__ lpeer, StartIO sio) {
   const int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (g >= s.G) return;
   const int lp = lpeer[g], k = sio.counts[g];
-  int idx = -1, term = -1, isl = 0, e = 0;
+  StartOutcome o{-1, -1, 0, 0};
   if (lp >= 0 && lp < s.P) {
-    const int64_t sl = g * s.P + lp;
-    if (k < 0) {
-      e = MRAFT_ITEM_BAD_SLOT;
-    } else if (k > 0 && s.role[sl] == kLeader) {                        // raft.go:93-95
-      const int last = s.last[sl], dummy = s.dummy[sl], t = s.term[sl], h = s.head[sl];
-      if ((int64_t)last + k - dummy > (int64_t)s.L - 1 || (int64_t)last + k > (int64_t)INT32_MAX - 1) {
-        e = MRAFT_ITEM_LOG_FULL;
-      } else {
-        if (last > dummy && s.log[sl * s.L + ring(last - dummy + h, s.L)] > t) s.srt[sl] = 0;
-        for (int j = 1; j <= k; ++j) s.log[sl * s.L + ring(last + j - dummy + h, s.L)] = t;  // :96-100
-        s.last[sl] = last + k;
-        mark_persist(s, sl, MRAFT_PERSIST_STATE);                        // :101
-        idx = last + 1; term = t; isl = 1;                               // :103
-      }
-    }
+    if (k < 0) o.err = MRAFT_ITEM_BAD_SLOT;
+    else if (k > 0) o = start_at(s, g * s.P + lp, k);
   } else if (lp >= s.P && k != 0) {
-    e = MRAFT_ITEM_BAD_SLOT;
+    o.err = MRAFT_ITEM_BAD_SLOT;
   }
-  sio.oi[g] = idx; sio.ot[g] = term; sio.ol[g] = isl; sio.err[g] = e;
+  sio.oi[g] = o.index; sio.ot[g] = o.term; sio.ol[g] = o.is_leader; sio.err[g] = o.err;
 }
 
 // ---------------------------------------------------------------- applier
@@ -175,42 +130,35 @@ __global__ void k_collect_apply(Dev s, int32_t *__restrict__ from, int32_t *__re
   const int64_t gp = (int64_t)s.G * s.P;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < gp;
        i += (int64_t)gridDim.x * blockDim.x) {
-    if (snap_index) {                                                  // raft.go:168-177
-      const bool hs = s.hsnap[i] != 0;
-      snap_index[i] = hs ? s.dummy[i] : -1;
-      snap_term[i] = hs ? s.log[i * s.L + s.head[i]] : 0;              // dummyTerm
-      if (hs) s.hsnap[i] = 0;
-    }
-    const int la = s.applied[i], ci = s.commit[i];
-    from[i] = la + 1;                                                  // raft.go:179-190
-    to[i] = ci;
-    if (ci > la) s.applied[i] = ci;                                    // :200
+    const ApplyMsg m = apply_slot(s, i, snap_index ? s.hsnap[i] : 0, s.applied[i], s.commit[i]);
+    if (snap_index) { snap_index[i] = m.snap_index; snap_term[i] = m.snap_term; }
+    from[i] = m.from; to[i] = m.to;
   }
 }
 
 // Compacted applier: slots with a message to send, ascending, in three
-// launches (per-block counts, one-workgroup exclusive scan, emit). `snaps`:
-// the caller takes SnapshotValid messages (hasSnapshot counts and is
-// cleared); without, only commitIndex > lastApplied counts and hasSnapshot
-// is left for a later call that takes them (as mraft_collect_apply does).
-__global__ __launch_bounds__(256) void k_apply_count(Dev s, int32_t *__restrict__ bcnt, int snaps) {
+// launches (mraft_device.h "ordered compaction", one list). `snaps`: the
+// caller takes SnapshotValid messages (hasSnapshot counts and is cleared);
+// without, only commitIndex > lastApplied counts and hasSnapshot is left for
+// a later call that takes them (as mraft_collect_apply does).
+__global__ __launch_bounds__(kCompactBlock) void k_apply_count(Dev s, int32_t *__restrict__ bcnt, int snaps) {
   const int64_t gp = (int64_t)s.G * s.P;
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const bool pend = i < gp && ((snaps && s.hsnap[i] != 0) || s.commit[i] > s.applied[i]);
-  const unsigned long long m = __ballot(pend);
-  __shared__ int wc[4];
-  if (lane_id() == 0) wc[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) bcnt[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+  const bool pend[1] = {i < gp && apply_pending(snaps ? s.hsnap[i] : 0, s.applied[i], s.commit[i])};
+  compact_count<1>(pend, bcnt, gridDim.x);
 }
 
-__global__ __launch_bounds__(1024) void k_apply_scan(int32_t *__restrict__ bcnt, int64_t nb,
-                                                     int64_t *__restrict__ total) {
+// The scan of every compaction: workgroup k scans list k's nb block counts in
+// place (exclusive), 1,024 at a time with a carry, and writes the list's
+// total (total0 for list 0, total1 for list 1).
+__global__ __launch_bounds__(1024) void k_compact_scan(int32_t *__restrict__ bcnt, int64_t nb,
+                                                       int64_t *__restrict__ total0, int64_t *__restrict__ total1) {
   __shared__ int64_t part[1024];
+  int32_t *c = bcnt + blockIdx.x * nb;
   int64_t carry = 0;
   for (int64_t base = 0; base < nb; base += 1024) {
     const int64_t i = base + threadIdx.x;
-    const int64_t v = i < nb ? bcnt[i] : 0;
+    const int64_t v = i < nb ? c[i] : 0;
     part[threadIdx.x] = v;
     __syncthreads();
     for (int o = 1; o < 1024; o <<= 1) {  // inclusive Hillis-Steele scan
@@ -219,49 +167,37 @@ __global__ __launch_bounds__(1024) void k_apply_scan(int32_t *__restrict__ bcnt,
       part[threadIdx.x] += add;
       __syncthreads();
     }
-    if (i < nb) bcnt[i] = (int32_t)(carry + part[threadIdx.x] - v);  // exclusive offset
+    if (i < nb) c[i] = (int32_t)(carry + part[threadIdx.x] - v);  // exclusive offset
     const int64_t chunk = part[1023];
     __syncthreads();
     carry += chunk;
   }
-  if (threadIdx.x == 0) *total = carry;
+  if (threadIdx.x == 0) *(blockIdx.x == 0 ? total0 : total1) = carry;
 }
 
-__global__ __launch_bounds__(256) void k_apply_emit(Dev s, const int32_t *__restrict__ boff, int64_t cap,
-                                                    int32_t *__restrict__ oslot, int32_t *__restrict__ osi,
-                                                    int32_t *__restrict__ ost, int32_t *__restrict__ ofrom,
-                                                    int32_t *__restrict__ oto) {
+__global__ __launch_bounds__(kCompactBlock) void k_apply_emit(
+    Dev s, const int32_t *__restrict__ boff, int64_t cap, int32_t *__restrict__ oslot, int32_t *__restrict__ osi,
+    int32_t *__restrict__ ost, int32_t *__restrict__ ofrom, int32_t *__restrict__ oto) {
   const int64_t gp = (int64_t)s.G * s.P;
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int la = 0, ci = 0, hs = 0;
   if (i < gp) { la = s.applied[i]; ci = s.commit[i]; hs = osi ? s.hsnap[i] : 0; }
-  const bool pend = i < gp && (hs != 0 || ci > la);
-  const unsigned long long m = __ballot(pend);
-  __shared__ int wc[4];
-  if (lane_id() == 0) wc[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  const int w = threadIdx.x >> 6;
-  int off = boff[blockIdx.x];
-  for (int k = 0; k < w; ++k) off += wc[k];
-  off += __popcll(m & ((1ull << lane_id()) - 1));
-  if (pend && off < cap) {
-    oslot[off] = (int32_t)i;
-    if (osi) {
-      osi[off] = hs ? s.dummy[i] : -1;                                 // raft.go:168-177
-      ost[off] = hs ? s.log[i * s.L + s.head[i]] : 0;                  // dummyTerm
-      if (hs) s.hsnap[i] = 0;
-    }
-    ofrom[off] = la + 1;                                               // raft.go:179-190
-    oto[off] = ci;
-    if (ci > la) s.applied[i] = ci;                                    // :200
+  const bool pend[1] = {i < gp && apply_pending(hs, la, ci)};
+  int64_t off[1];
+  compact_offsets<1>(pend, boff, gridDim.x, off);
+  if (pend[0] && off[0] < cap) {
+    const ApplyMsg m = apply_slot(s, i, hs, la, ci);
+    oslot[off[0]] = (int32_t)i;
+    if (osi) { osi[off[0]] = m.snap_index; ost[off[0]] = m.snap_term; }
+    ofrom[off[0]] = m.from; oto[off[0]] = m.to;
   }
 }
 
 // ---------------------------------------------------------------- snapshots
-// Snapshot (raft_snapshot.go:3-13): wave per item.
-// Snapshot: setLogs(sliceFrom(index)) (raft_snapshot.go:10, raft_log.go:18-21,
-// 75-77) is an O(1) rebase of the ring — the head moves to the entry at
-// `index`, which becomes the dummy with its own term; no term moves.
+// Snapshot (raft_snapshot.go:3-13), thread per item: setLogs(sliceFrom(index))
+// (:10, raft_log.go:18-21, 75-77) is an O(1) rebase of the ring — the head
+// moves to the entry at `index`, which becomes the dummy with its own term;
+// no term moves.
 __global__ __launch_bounds__(256) void k_snapshot(Dev s, const int32_t *__restrict__ slots,
                                                   const int32_t *__restrict__ index, int64_t n,
                                                   int32_t *__restrict__ err) {
@@ -304,44 +240,26 @@ __global__ void k_gather_is(Dev s, const int32_t *__restrict__ slots, const int3
   err[i] = e;
 }
 
-// HandleInstallSnapshot (raft_snapshot.go:15-54): wave per item.
 // HandleInstallSnapshot (raft_snapshot.go:15-54), thread per item. Installing
 // by sliceFrom(LastIncludedIndex) (:38-40) is an O(1) ring rebase.
-__global__ __launch_bounds__(256) void k_handle_is(Dev s, const mraft_is_args *__restrict__ args,
-                                                   int64_t n, mraft_is_reply *__restrict__ rep,
-                                                   int32_t *__restrict__ flags,
+__global__ __launch_bounds__(256) void k_handle_is(Dev s, const mraft_is_args *__restrict__ args, int64_t n,
+                                                   mraft_is_reply *__restrict__ rep, int32_t *__restrict__ flags,
                                                    int32_t *__restrict__ err) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (err[i]) {
-    rep[i] = mraft_is_reply{0, 0};
-    flags[i] = 0;
-    return;
-  }
+  // every exit: the reply's term, the flags and, for an item refused here, its error
+  auto out = [&](int term, int fl, int e = 0) { rep[i] = mraft_is_reply{term, 0}; flags[i] = fl; if (e) err[i] = e; };
+  if (err[i]) return out(0, 0);
   const mraft_is_args a = args[i];
-  if (a.last_included_index > INT32_MAX - 1) {  // past the Index domain (include/mraft.h): malformed
-    rep[i] = mraft_is_reply{0, 0};
-    flags[i] = 0;
-    err[i] = MRAFT_ITEM_BAD_SLOT;
-    return;
-  }
+  if (!index_in_domain(a.last_included_index)) return out(0, 0, MRAFT_ITEM_BAD_SLOT);  // malformed
   const int f = a.slot, fterm = s.term[f];
-  int fl = 0;
-  if (a.term < fterm) {                                                // :20-22
-    rep[i] = mraft_is_reply{fterm, 0};
-    flags[i] = 0;
-    return;
-  }
+  if (a.term < fterm) return out(fterm, 0);                            // :20-22
   const int lii = a.last_included_index;
   const int fcommit = s.commit[f];
   const bool install = lii > fcommit;                                  // :31-33
   const int fd = s.dummy[f], flast = s.last[f], fh = s.head[f];
-  if (install && lii <= flast && lii < fd) {                           // sliceFrom panics
-    rep[i] = mraft_is_reply{0, 0};
-    flags[i] = 0;
-    err[i] = MRAFT_ITEM_BELOW_DUMMY;
-    return;
-  }
+  if (install && lii <= flast && lii < fd) return out(0, 0, MRAFT_ITEM_BELOW_DUMMY);  // sliceFrom panics
+  int fl = 0;
   if (a.term > fterm) { s.term[f] = a.term; s.voted[f] = -1; }         // :23-26
   s.role[f] = kFollower;                                               // :28
   if (install) {
@@ -358,33 +276,26 @@ __global__ __launch_bounds__(256) void k_handle_is(Dev s, const mraft_is_args *_
   }
   mark_persist(s, f, (a.term > fterm ? MRAFT_PERSIST_STATE : 0) |     // :26
                          (install ? MRAFT_PERSIST_STATE | MRAFT_PERSIST_SNAPSHOT : 0));  // :47
-  rep[i] = mraft_is_reply{a.term, 0};                                  // deferred reply.Term
-  flags[i] = fl;
+  out(a.term, fl);                                                     // deferred reply.Term
 }
 
 // processInstallSnapshotReply (raft_snapshot.go:56-69): lane per segment.
-__global__ void k_process_is(Dev s, const mraft_is_result *__restrict__ items, int64_t n,
-                             const int64_t *__restrict__ seg_begin, int64_t n_seg,
-                             const int32_t *__restrict__ seg_err, int32_t *__restrict__ flags,
+__global__ void k_process_is(Dev s, const mraft_is_result *__restrict__ items, const int64_t *__restrict__ seg_begin,
+                             int64_t n_seg, const int32_t *__restrict__ seg_err, int32_t *__restrict__ flags,
                              int32_t *__restrict__ item_err) {
   const int64_t sg = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (sg >= n_seg) return;
-  const int64_t b = seg_begin ? seg_begin[sg] : sg, e = seg_begin ? seg_begin[sg + 1] : sg + 1;
-  if (b >= e) return;
+  int64_t b, e;
+  if (!segment_bounds(seg_begin, sg, b, e)) return;
   const int P = s.P;
-  const int slot = items[b].slot;
-  int bad = seg_err[sg];
-  if (!bad)
-    for (int64_t i = b; i < e; ++i) {
-      const mraft_is_result it = items[i];
-      if (it.slot != slot || it.peer < 0 || it.peer >= P || it.peer == slot % P ||
-          it.args_last_included_index > INT32_MAX - 1)  // (past the Index domain, include/mraft.h)
-        bad = MRAFT_ITEM_BAD_SLOT;
-    }
+  const int bad = segment_verdict(items, b, e, P, seg_err[sg], [](const mraft_is_result &it) {
+    return index_in_domain(it.args_last_included_index);
+  });
   if (bad) {
-    for (int64_t i = b; i < e; ++i) { item_err[i] = bad; flags[i] = 0; }
+    segment_reject(b, e, bad, flags, item_err);
     return;
   }
+  const int slot = items[b].slot;
   int term = s.term[slot], role = s.role[slot];
   const int t0 = term;
   for (int64_t i = b; i < e; ++i) {
@@ -466,27 +377,20 @@ __global__ void k_handle_rv(Dev s, const mraft_rv_args *__restrict__ args, int64
 }
 
 // ---------------------------------------------------------------- a6 part 2
-__global__ void k_tally(Dev s, const mraft_rv_result *__restrict__ items, int64_t n,
-                        const int64_t *__restrict__ seg_begin, int64_t n_seg,
-                        const int32_t *__restrict__ seg_err, int32_t *__restrict__ flags,
+__global__ void k_tally(Dev s, const mraft_rv_result *__restrict__ items, const int64_t *__restrict__ seg_begin,
+                        int64_t n_seg, const int32_t *__restrict__ seg_err, int32_t *__restrict__ flags,
                         int32_t *__restrict__ item_err) {
   const int64_t sg = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (sg >= n_seg) return;
-  const int64_t b = seg_begin ? seg_begin[sg] : sg, e = seg_begin ? seg_begin[sg + 1] : sg + 1;
-  if (b >= e) return;
+  int64_t b, e;
+  if (!segment_bounds(seg_begin, sg, b, e)) return;
   const int P = s.P;
-  const int c = items[b].slot;
-  int bad = seg_err[sg];
-  if (!bad) {
-    for (int64_t i = b; i < e; ++i) {
-      const mraft_rv_result it = items[i];
-      if (it.slot != c || it.peer < 0 || it.peer >= P || it.peer == c % P) bad = MRAFT_ITEM_BAD_SLOT;
-    }
-  }
+  const int bad = segment_verdict(items, b, e, P, seg_err[sg], [](const mraft_rv_result &) { return true; });
   if (bad) {
-    for (int64_t i = b; i < e; ++i) { item_err[i] = bad; flags[i] = 0; }
+    segment_reject(b, e, bad, flags, item_err);
     return;
   }
+  const int c = items[b].slot;
   int term = s.term[c], role = s.role[c], votes = s.votes[c], voted = s.voted[c];
   const int t0 = term, r0 = role, vs0 = votes, vd0 = voted;
   bool lead = false, stepped = false;
@@ -609,7 +513,14 @@ __global__ void k_export(Dev s, const int32_t *__restrict__ lpeer, int32_t *__re
   if (p < 0 || p >= s.P) p = 0;
   const int64_t sl = (int64_t)g * s.P + p;
   commit[g] = s.commit[sl];
-  term_leader[g] = (int32_t)(((uint32_t)s.term[sl] << 1) | (s.role[sl] == kLeader ? 1u : 0u));  // raft.go:237-246
+  term_leader[g] = term_leader_word(s.term[sl], s.role[sl]);
+}
+
+// Launchers. A thread per item in workgroups of B threads; nothing to do without items.
+template <int B = kBlock, class K, class... A>
+void launch_items(K k, int64_t n, hipStream_t st, A... a) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k, dim3(blocks_for(n, B)), dim3(B), 0, st, a...);
 }
 
 }  // namespace
@@ -625,37 +536,26 @@ void launch_init_state(const Dev &s, hipStream_t st) {
   hipLaunchKernelGGL(k_init_state, dim3(blocks_strided((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s);
 }
 
-void launch_claim(const void *items, int64_t n, int stride, int slot_off, const int64_t *seg_begin,
-                  int64_t gp, int peers, unsigned long long *claim, uint32_t epoch, int32_t *err,
-                  hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_claim, dim3(blocks_for(n)), dim3(kBlock), 0, st, (const char *)items, n,
-                     stride, slot_off, seg_begin, gp, peers, claim, epoch, err);
-  hipLaunchKernelGGL(k_claim_check, dim3(blocks_for(n)), dim3(kBlock), 0, st, (const char *)items,
-                     n, stride, slot_off, seg_begin, claim, epoch, err);
+void launch_claim(const void *items, int64_t n, int stride, int slot_off, const int64_t *seg_begin, int64_t gp,
+                  unsigned long long *claim, uint32_t epoch, int32_t *err, hipStream_t st) {
+  launch_items(k_claim, n, st, (const char *)items, n, stride, slot_off, seg_begin, gp, claim, epoch, err);
+  launch_items(k_claim_check, n, st, (const char *)items, n, stride, slot_off, seg_begin, claim, epoch, err);
 }
 
-void launch_gather_args(const Dev &s, const int32_t *slots, const int32_t *peers, int64_t n,
-                        mraft_ae_args *out, int32_t *err, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_gather_args, dim3(blocks_for(n, kMsgBlock)), dim3(kMsgBlock), 0, st, s, slots, peers, n,
-                     out, err);
+void launch_gather_args(const Dev &s, const int32_t *slots, const int32_t *peers, int64_t n, mraft_ae_args *out,
+                        int32_t *err, hipStream_t st) {
+  launch_items<kMsgBlock>(k_gather_args, n, st, s, slots, peers, n, out, err);
 }
 
-void launch_start(const Dev &s, const int32_t *slots, const int32_t *counts, int64_t n, int32_t *oi,
-                  int32_t *ot, int32_t *ol, int32_t *err, const unsigned long long *claim, uint32_t epoch,
-                  hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_claim, dim3(blocks_for(n)), dim3(kBlock), 0, st, (const char *)slots, n, (int)sizeof(int32_t),
-                     0, (const int64_t *)nullptr, (int64_t)s.G * s.P, s.P, const_cast<unsigned long long *>(claim),
-                     epoch, err);
-  hipLaunchKernelGGL(k_start, dim3(blocks_for(n)), dim3(kBlock), 0, st, s, slots, counts, n, oi, ot,
-                     ol, err, claim, epoch);
+void launch_start(const Dev &s, const int32_t *slots, const int32_t *counts, int64_t n, int32_t *oi, int32_t *ot,
+                  int32_t *ol, int32_t *err, unsigned long long *claim, uint32_t epoch, hipStream_t st) {
+  launch_items(k_claim, n, st, (const char *)slots, n, (int)sizeof(int32_t), 0, (const int64_t *)nullptr,
+               (int64_t)s.G * s.P, claim, epoch, err);
+  launch_items(k_start, n, st, s, slots, counts, n, oi, ot, ol, err, claim, epoch);
 }
 
 void launch_start_groups(const Dev &s, const int32_t *lpeer, const StartIO &sio, hipStream_t st) {
-  if (s.G <= 0) return;
-  hipLaunchKernelGGL(k_start_groups, dim3(blocks_for(s.G)), dim3(kBlock), 0, st, s, lpeer, sio);
+  launch_items(k_start_groups, s.G, st, s, lpeer, sio);
 }
 
 void launch_collect_apply(const Dev &s, int32_t *from, int32_t *to, int32_t *snap_index, int32_t *snap_term,
@@ -664,95 +564,76 @@ void launch_collect_apply(const Dev &s, int32_t *from, int32_t *to, int32_t *sna
                      snap_index, snap_term);
 }
 
+void launch_compact_scan(int32_t *bcnt, int64_t nb, int lists, int64_t *total0, int64_t *total1, hipStream_t st) {
+  hipLaunchKernelGGL(k_compact_scan, dim3(lists), dim3(1024), 0, st, bcnt, nb, total0, total1);
+}
+
 void launch_collect_apply_compact(const Dev &s, int32_t *scratch_bcnt, int64_t cap, int32_t *oslot,
                                   int32_t *osnap_index, int32_t *osnap_term, int32_t *ofrom, int32_t *oto,
                                   int64_t *total, hipStream_t st) {
-  const int64_t gp = (int64_t)s.G * s.P;
-  const int64_t nb = (gp + 255) / 256;
-  hipLaunchKernelGGL(k_apply_count, dim3((unsigned)nb), dim3(256), 0, st, s, scratch_bcnt,
+  const int64_t nb = compact_blocks((int64_t)s.G * s.P);
+  hipLaunchKernelGGL(k_apply_count, dim3((unsigned)nb), dim3(kCompactBlock), 0, st, s, scratch_bcnt,
                      osnap_index ? 1 : 0);
-  hipLaunchKernelGGL(k_apply_scan, dim3(1), dim3(1024), 0, st, scratch_bcnt, nb, total);
-  hipLaunchKernelGGL(k_apply_emit, dim3((unsigned)nb), dim3(256), 0, st, s, scratch_bcnt, cap, oslot,
+  launch_compact_scan(scratch_bcnt, nb, 1, total, nullptr, st);
+  hipLaunchKernelGGL(k_apply_emit, dim3((unsigned)nb), dim3(kCompactBlock), 0, st, s, scratch_bcnt, cap, oslot,
                      osnap_index, osnap_term, ofrom, oto);
 }
 
-void launch_snapshot(const Dev &s, const int32_t *slots, const int32_t *index, int64_t n,
-                     int32_t *err, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_snapshot, dim3(blocks_for(n)), dim3(kBlock), 0, st, s, slots, index, n, err);
+void launch_snapshot(const Dev &s, const int32_t *slots, const int32_t *index, int64_t n, int32_t *err,
+                     hipStream_t st) {
+  launch_items(k_snapshot, n, st, s, slots, index, n, err);
 }
 
-void launch_gather_is(const Dev &s, const int32_t *slots, const int32_t *peers, int64_t n,
-                      mraft_is_args *out, int32_t *err, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_gather_is, dim3(blocks_for(n)), dim3(kBlock), 0, st, s, slots, peers, n, out, err);
-}
-
-void launch_handle_is(const Dev &s, const mraft_is_args *args, int64_t n, mraft_is_reply *rep,
-                      int32_t *flags, int32_t *err, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_handle_is, dim3(blocks_for(n)), dim3(kBlock), 0, st, s, args, n, rep,
-                     flags, err);
-}
-
-void launch_process_is(const Dev &s, const mraft_is_result *items, int64_t n, const int64_t *seg_begin,
-                       int64_t n_seg, int32_t *seg_err, int32_t *flags, int32_t *item_err,
-                       hipStream_t st) {
-  (void)n;
-  if (n_seg <= 0) return;
-  hipLaunchKernelGGL(k_process_is, dim3(blocks_for(n_seg, 64)), dim3(64), 0, st, s, items, n,
-                     seg_begin, n_seg, seg_err, flags, item_err);
-}
-
-void launch_start_election(const Dev &s, const int32_t *slots, int64_t n, mraft_rv_args *out,
-                           int32_t *err, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_start_election, dim3(blocks_for(n)), dim3(kBlock), 0, st, s, slots, n, out,
-                     err);
-}
-
-void launch_handle_rv(const Dev &s, const mraft_rv_args *args, int64_t n, mraft_rv_reply *rep,
+void launch_gather_is(const Dev &s, const int32_t *slots, const int32_t *peers, int64_t n, mraft_is_args *out,
                       int32_t *err, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_handle_rv, dim3(blocks_for(n)), dim3(kBlock), 0, st, s, args, n, rep, err);
+  launch_items(k_gather_is, n, st, s, slots, peers, n, out, err);
 }
 
-void launch_tally(const Dev &s, const mraft_rv_result *items, int64_t n, const int64_t *seg_begin,
-                  int64_t n_seg, int32_t *seg_err, int32_t *flags, int32_t *item_err,
-                  hipStream_t st) {
-  (void)n;
-  if (n_seg <= 0) return;
-  hipLaunchKernelGGL(k_tally, dim3(blocks_for(n_seg, 64)), dim3(64), 0, st, s, items, n, seg_begin,
-                     n_seg, seg_err, flags, item_err);
+void launch_handle_is(const Dev &s, const mraft_is_args *args, int64_t n, mraft_is_reply *rep, int32_t *flags,
+                      int32_t *err, hipStream_t st) {
+  launch_items(k_handle_is, n, st, s, args, n, rep, flags, err);
+}
+
+void launch_process_is(const Dev &s, const mraft_is_result *items, const int64_t *seg_begin, int64_t n_seg,
+                       int32_t *seg_err, int32_t *flags, int32_t *item_err, hipStream_t st) {
+  launch_items<64>(k_process_is, n_seg, st, s, items, seg_begin, n_seg, seg_err, flags, item_err);
+}
+
+void launch_start_election(const Dev &s, const int32_t *slots, int64_t n, mraft_rv_args *out, int32_t *err,
+                           hipStream_t st) {
+  launch_items(k_start_election, n, st, s, slots, n, out, err);
+}
+
+void launch_handle_rv(const Dev &s, const mraft_rv_args *args, int64_t n, mraft_rv_reply *rep, int32_t *err,
+                      hipStream_t st) {
+  launch_items(k_handle_rv, n, st, s, args, n, rep, err);
+}
+
+void launch_tally(const Dev &s, const mraft_rv_result *items, const int64_t *seg_begin, int64_t n_seg,
+                  int32_t *seg_err, int32_t *flags, int32_t *item_err, hipStream_t st) {
+  launch_items<64>(k_tally, n_seg, st, s, items, seg_begin, n_seg, seg_err, flags, item_err);
 }
 
 void launch_collect_persist(const Dev &s, int32_t *out, hipStream_t st) {
   hipLaunchKernelGGL(k_collect_persist, dim3(blocks_strided((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s, out);
 }
 
-void launch_read_persistent_hdr(const Dev &s, const int32_t *slots, int64_t n,
-                                mraft_persistent *out, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_read_persistent_hdr, dim3(blocks_for(n)), dim3(kBlock), 0, st, s, slots, n, out);
+void launch_read_persistent_hdr(const Dev &s, const int32_t *slots, int64_t n, mraft_persistent *out, hipStream_t st) {
+  launch_items(k_read_persistent_hdr, n, st, s, slots, n, out);
 }
 
-void launch_read_persistent_terms(const Dev &s, const mraft_persistent *hdr, int64_t n,
-                                  int32_t *out, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_read_persistent_terms, dim3(blocks_for(n * 64)), dim3(kBlock), 0, st, s, hdr,
-                     n, out);
+// (a wave per item: 64 threads each)
+void launch_read_persistent_terms(const Dev &s, const mraft_persistent *hdr, int64_t n, int32_t *out, hipStream_t st) {
+  launch_items(k_read_persistent_terms, n * 64, st, s, hdr, n, out);
 }
 
-void launch_restore(const Dev &s, const mraft_persistent *in, int64_t n, const int32_t *terms,
-                    const int32_t *err, hipStream_t st) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_restore, dim3(blocks_for(n * 64)), dim3(kBlock), 0, st, s, in, n, terms, err);
+void launch_restore(const Dev &s, const mraft_persistent *in, int64_t n, const int32_t *terms, const int32_t *err,
+                    hipStream_t st) {
+  launch_items(k_restore, n * 64, st, s, in, n, terms, err);
 }
 
-void launch_export(const Dev &s, const int32_t *lpeer, int32_t *commit, int32_t *term_leader,
-                   hipStream_t st) {
-  hipLaunchKernelGGL(k_export, dim3(blocks_for(s.G)), dim3(kBlock), 0, st, s, lpeer, commit,
-                     term_leader);
+void launch_export(const Dev &s, const int32_t *lpeer, int32_t *commit, int32_t *term_leader, hipStream_t st) {
+  launch_items(k_export, s.G, st, s, lpeer, commit, term_leader);
 }
 
 }  // namespace mraft

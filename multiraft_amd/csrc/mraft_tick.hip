@@ -33,6 +33,7 @@
 #include "mraft_device.h"
 #include "mraft_internal.h"
 #include "mraft_pass.h"
+#include "mraft_rules.h"
 
 namespace mraft {
 
@@ -206,7 +207,7 @@ struct Export {
   __device__ __forceinline__ void put(int g, int c, int t, int role) const {
     if (commit) {
       commit[g] = c;
-      term_leader[g] = (int32_t)(((uint32_t)t << 1) | (role == kLeader ? 1u : 0u));
+      term_leader[g] = term_leader_word(t, role);
     }
   }
 };
@@ -218,15 +219,10 @@ __global__ __launch_bounds__(64, MRAFT_TICK_MINW) void k_tick_group(Dev s, const
                                                     Export ex) {
   constexpr int NI = P - 1;
   const int lane = lane_id();
-  // Blocks are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md
-  // §Workgroup dispatch): give each XCD a contiguous range of groups so the
-  // scalar SoA lines neighbouring groups share stay in one XCD's L2. Speed
-  // only; any placement gives the same results.
-  int gb = (int)blockIdx.x;
-  {
-    const int nb = (int)gridDim.x, x = gb & 7, per = nb >> 3, rem = nb & 7;
-    gb = x * per + min(x, rem) + (gb >> 3);
-  }
+  // Each XCD a contiguous range of groups, so the scalar SoA lines
+  // neighbouring groups share stay in one XCD's L2. Speed only; any placement
+  // gives the same results.
+  const int gb = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
   // (threadIdx.x >> 6 is 0 in a one-wave workgroup; without the term the
   // compiler assigns this kernel's registers differently, so the measured
   // code is kept instruction-for-instruction)
@@ -290,7 +286,8 @@ constexpr int kLiteWaves = 4;  // waves per light workgroup: 32 groups, one list
 
 // START (mraft_start_and_tick): Start (raft.go:90-104) of counts[g] entries at
 // the group's leader replica first, inside this launch: the leader lane
-// appends them (terms_sorted, lastIndex, persist bit, as k_start) and the
+// appends them (start_fits, then terms_sorted, lastIndex and the persist bit
+// as start_at does, mraft_rules.h: here spread over lanes and round trips) and the
 // tick runs on the result — the new entries' terms are currentTerm, known
 // without a load (the followers' copies and a1's probe of the new last).
 // Groups that fall back carry their Start's stores into the full tick.
@@ -303,11 +300,7 @@ __global__ __launch_bounds__(64 * kLiteWaves, 8) void k_tick_lite(Dev s, const i
   __shared__ unsigned sh_cnt, sh_base;
   const int lane = lane_id(), j = lane & 7, gbase = lane & ~7, wv = (int)(threadIdx.x >> 6);
   const int xcd = (int)(blockIdx.x & 7);
-  int wb = (int)blockIdx.x;  // XCD-contiguous workgroup ranges, as k_tick_group
-  {
-    const int nb = (int)gridDim.x, x = wb & 7, per = nb >> 3, rem = nb & 7;
-    wb = x * per + min(x, rem) + (wb >> 3);
-  }
+  const int wb = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);  // as k_tick_group
   if (threadIdx.x == 0) sh_cnt = 0;
   const int g = (wb * kLiteWaves + wv) * 8 + (lane >> 3);
   const bool live = g < s.G;
@@ -343,7 +336,7 @@ __global__ __launch_bounds__(64 * kLiteWaves, 8) void k_tick_lite(Dev s, const i
   const int lp = go ? lpv : 0;
   const int role = bc(rrole, lp), T = bc(rterm, lp), c0 = bc(rcommit, lp), last0 = bc(rlast, lp),
             ldummy = bc(rdummy, lp), lhead = bc(rhead, lp), lsrt0 = bc(rsrt, lp);
-  // START: mraft_start's decision (k_start) for the group's leader replica
+  // START: mraft_start's decision (k_start_groups' preamble, start_fits) for the group's leader replica
   bool started = false;
   int serr = 0;
   if (START && live) {
@@ -351,10 +344,8 @@ __global__ __launch_bounds__(64 * kLiteWaves, 8) void k_tick_lite(Dev s, const i
       if (kcnt < 0) {
         serr = MRAFT_ITEM_BAD_SLOT;
       } else if (kcnt > 0 && role == kLeader) {                          // raft.go:93-95
-        if ((int64_t)last0 + kcnt - ldummy > (int64_t)L - 1 || (int64_t)last0 + kcnt > (int64_t)INT32_MAX - 1)
-          serr = MRAFT_ITEM_LOG_FULL;
-        else
-          started = true;
+        started = start_fits(last0, kcnt, ldummy, L);
+        if (!started) serr = MRAFT_ITEM_LOG_FULL;
       }
     } else if (lpv >= P && kcnt != 0) {
       serr = MRAFT_ITEM_BAD_SLOT;

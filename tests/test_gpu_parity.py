@@ -478,12 +478,12 @@ def test_applier_compact_snapshot_outputs_gpu():
 
 
 APPLY_BLOCK = 256    # slots per block of k_apply_count / k_apply_emit (their launch's blockDim)
-APPLY_CHUNK = 1024   # block counts per chunk of k_apply_scan (its part[1024])
+APPLY_CHUNK = 1024   # block counts per chunk of k_compact_scan (its part[1024])
 
 
 def _apply_scan_state(snaps):
     """262,155 slots = 1,025 blocks of 256: block 1,024 is the one block of
-    k_apply_scan's second chunk, so its offsets are the running total carried
+    k_compact_scan's second chunk, so its offsets are the running total carried
     out of the first. commitIndex > lastApplied (and, with `snaps`,
     hasSnapshot alone) set directly: the first and last slot of blocks 0,
     1,023 and 1,024, one slot mid-block in each chunk, a sparse background."""
@@ -517,7 +517,7 @@ def _apply_scan_state(snaps):
 
 @pytest.mark.parametrize("variant", ["unlimited", "cap", "snapshots"])
 def test_applier_compact_second_scan_chunk_gpu(variant):
-    """The compacted applier where k_apply_scan runs a second chunk: count,
+    """The compacted applier where k_compact_scan runs a second chunk: count,
     ascending slots and ranges against the dense oracle; with a cap that ends
     inside block 1,024 only the listed slots advance, the second call returns
     the remainder, a third nothing."""

@@ -122,6 +122,33 @@ def test_tiny_engines_gpu(G, P):
         _run(listed, shards, TICK_LIGHT, path=True)
 
 
+@pytest.mark.parametrize("L", [37, 64])
+@pytest.mark.parametrize("P", [2, 5])
+@pytest.mark.parametrize("name", ["B-mixed", "C-mixed", "C-top-light", "bad-slot"])
+def test_directed_start_items_gpu(name, P, L):
+    """The directed Start cases through the item-level mraft_start (k_start),
+    which shares Start's rule with mraft_start_and_tick's two kernels: the
+    groups oracle_start_and_tick selects (leader_peer in range, counts != 0)
+    as one call of slots and counts, against the case's intended outputs
+    (both sides of the ring's capacity and of the Index domain, negative
+    counts), the oracle's Start, and the whole state."""
+    c = lc.bad_slot_case(P, L) if name == "bad-slot" else lc.case(name, P, L)
+    G, lp = c.G, c.leader_peer
+    ctx = f"{name} P={P} L={L} mraft_start"
+    sel = np.flatnonzero((lp >= 0) & (lp < P) & (c.counts != 0))
+    assert len(sel)
+    slots, cnt = (sel * P + lp[sel]).astype(np.int32), c.counts[sel].astype(np.int32)
+    o = Oracle(G, P, L, c.state)
+    with Engine(G, P, L) as e:
+        e.load_state(c.state)
+        outs = e.start(slots, cnt)
+        oouts = o.start(slots, cnt)
+        for a, want, b, nm in zip(outs, c.start_expect, oouts, START_NAMES):
+            assert np.array_equal(a, want[sel]), f"{ctx}: intended Start {nm} at {np.flatnonzero(a != want[sel])[:8]}"
+            assert np.array_equal(a, b), f"{ctx}: Start {nm} at {np.flatnonzero(a != b)[:8]}"
+        assert_states_equal(e.store_state(), o.state(), G, P, L, ctx)
+
+
 @pytest.mark.parametrize("mode", [TICK_LIGHT, TICK_FULL])
 @pytest.mark.parametrize("P", lc.PEERS)
 def test_negative_counts_gpu(P, mode):
