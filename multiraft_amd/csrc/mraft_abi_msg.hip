@@ -58,31 +58,31 @@ int mraft_handle_append_entries_ex(mraft_engine *h, const mraft_ae_args *args, i
   }
   // Entries by reference into the engine's log: the claims with the set
   // heads, the main launch, the deferred launch — three launches, every count
-  // they need stays on the device, nothing waits on the host (mraft_handle_ae.hip
+  // they need stays on the device, nothing waits on the host (mraft_handle_ae.h
   // "a4" for the rules).
   if (!h->ae_total) TRY(alloc_async(h, &h->ae_total, mraft::kAeTotalWords, "AppendEntries counters", true));
-  const size_t nn = (size_t)n, L = (size_t)h->L;
-  int64_t *soff, *defer;
+  const size_t nn = (size_t)n;
+  mraft::HsArgs ka{};
+  ka.s = dev_of(h); ka.args = a; ka.n = n; ka.rep = r; ka.err = e; ka.res = rs;
+  ka.total = h->ae_total; ka.claim = h->claim; ka.srcmark = h->srcmark; ka.epoch = h->epoch;
   uint8_t *sethd;
-  TRY(scratch(h, kScrAeSoff, nn, &soff));
+  TRY(scratch(h, kScrAeSoff, nn, &ka.soff));
   TRY(scratch(h, kScrAeSetHead, nn, &sethd));
-  TRY(scratch(h, kScrAeDefer, nn * mraft::kAeStripes, &defer));  // a list of n per stripe
+  ka.sethd = sethd;
+  TRY(scratch(h, kScrAeDefer, nn * mraft::kAeStripes, &ka.defer));  // a list of n per stripe
   // the deferred launch's grid: the last call's deferred count (a pinned word
   // the device writes; a stale value only changes the grid, never a result)
   const long long last_nd = hint(h, kHintDeferred);
-  mraft::AeDeferBufs db{};
   const long long gmin = h->defer_grid_min;
-  db.grid = (int)(last_nd < gmin ? gmin : last_nd > kDeferGridMax ? kDeferGridMax : last_nd);
-  db.nslot = (int)std::min<int64_t>(db.grid, std::max<int64_t>(1, kCycSlotWords / h->L));
-  // the fallback's per-item records and reader counts, its L-word buffer and
-  // nslot cycle buffers
+  const int grid = (int)(last_nd < gmin ? gmin : last_nd > kDeferGridMax ? kDeferGridMax : last_nd);
+  ka.nslot = (int)std::min<int64_t>(grid, std::max<int64_t>(1, kCycSlotWords / h->L));
+  // the fallback's per-item records, its L-word buffer and nslot cycle
+  // buffers, and its reader counts
   void *order;
-  TRY(scratch_bytes(h, kScrAeOrder, nn * 16 + (1 + (size_t)db.nslot) * L * 4, &order));
-  TRY(scratch_zeroed(h, kScrAeKin, nn, &db.kin));  // epoch-tagged: a buffer of its own, zeroed when new
-  db.fb = (int4 *)order;
-  db.cyc = (int32_t *)(db.fb + nn);
-  db.cslot = db.cyc + L;
-  db.hint = h->dhint_dev;
+  TRY(scratch_bytes(h, kScrAeOrder, mraft::ae_order_carve(ka, nullptr), &order));
+  mraft::ae_order_carve(ka, order);
+  TRY(scratch_zeroed(h, kScrAeKin, nn, &ka.kin));  // epoch-tagged: a buffer of its own, zeroed when new
+  ka.hint = h->dhint_dev;
   // MRAFT_STAGE_AUTO: a batch that exceeded the stage (its need published by
   // the device, kHintStageNeed) grows it for the calls after it (stream-ordered)
   if (h->stage_auto) {
@@ -93,17 +93,16 @@ int mraft_handle_append_entries_ex(mraft_engine *h, const mraft_ae_args *args, i
   // the stage: when it cannot be allocated the batch runs with none (every
   // staged item then takes the ordered fallback: the same results, slower);
   // an automatic stage stops growing there
-  int32_t *stage = nullptr;
-  if (h->stage_cap > 0 && scratch(h, kScrAeStage, (size_t)h->stage_cap, &stage) != MRAFT_OK) {
-    stage = nullptr;
+  if (h->stage_cap > 0 && scratch(h, kScrAeStage, (size_t)h->stage_cap, &ka.stage) != MRAFT_OK) {
+    ka.stage = nullptr;
     h->stage_auto = false;
   }
+  ka.stage_cap = ka.stage ? h->stage_cap : 0;
   const int ni = h->P - 1 < 1 ? 1 : h->P - 1 > 7 ? 7 : h->P - 1;
   const int64_t n_log = gp_of(h) * h->L;
   mraft::launch_claim_ae(a, n, n_log, h->L, gp_of(h), ni, h->claim, h->srcmark, h->epoch, e, sethd, h->ae_total,
                          h->stream);
-  mraft::launch_handle_ae_ref(dev_of(h), a, n, ni, h->claim, h->srcmark, h->epoch, e, sethd, soff, defer, h->ae_total,
-                              stage, stage ? h->stage_cap : 0, db, r, rs, h->stream);
+  mraft::launch_handle_ae_ref(ka, ni, grid, h->stream);
   return sg.finish();
 }
 

@@ -13,8 +13,7 @@ int32_t *off(int32_t *p, int64_t k) { return p ? p + k : nullptr; }
 // stream-ordered, counters zeroed.
 int ensure_lite(mraft_engine *h) {
   if (h->lite_list) return MRAFT_OK;
-  // a shard of G_s groups needs lite_list_words(G_s) <= G_s + 512 words
-  TRY(alloc_async(h, &h->lite_list, (size_t)h->G + 512 * kMaxShards, "light tick list"));
+  TRY(alloc_async(h, &h->lite_list, (size_t)mraft::lite_list_alloc_words(h->G, kMaxShards), "light tick list"));
   TRY(alloc_async(h, &h->lite_cnt, (size_t)2 * kMaxShards * mraft::kLiteCntWords, "light tick counters", true));
   for (int s = 0; s < kMaxShards; ++s) h->lite_par[s] = 0;
   return MRAFT_OK;
@@ -55,7 +54,7 @@ void tick_range(mraft_engine *h, const mraft::Dev &d, int s, int32_t g0, const i
   mraft::LiteBufs lb;
   const int par = h->lite_par[s];
   h->lite_par[s] ^= 1;
-  lb.list = h->lite_list + g0 + 512 * s;
+  lb.list = h->lite_list + mraft::lite_list_begin(g0, s);
   lb.cnt = h->lite_cnt + (2 * s + par) * mraft::kLiteCntWords;
   lb.cnt_next = h->lite_cnt + (2 * s + (par ^ 1)) * mraft::kLiteCntWords;
   lb.hint = h->dhint_dev + kHintLite + s;

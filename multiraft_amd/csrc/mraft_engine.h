@@ -115,7 +115,7 @@ struct mraft_engine {
   unsigned long long *claim = nullptr;
   uint32_t *srcmark = nullptr;             // per slot: epoch of the last call that read its row
   uint32_t epoch = 0;
-  unsigned long long *ae_total = nullptr;  // AppendEntries by reference: the deferred launch's counters (mraft_handle_ae.hip)
+  unsigned long long *ae_total = nullptr;  // AppendEntries by reference: the handler's counters (mraft_internal.h kAeCnt*)
   int64_t stage_cap = kDefaultStageWords;  // words of staged entries the deferred launch may use
   bool stage_auto = true;                  // MRAFT_STAGE_AUTO: grow stage_cap to the last overflow's need
   volatile long long *dhint = nullptr;  // the pinned host words (Hint): device-written
@@ -124,7 +124,7 @@ struct mraft_engine {
   // MRAFT_DEFER_GRID_MIN at mraft_create (tests run the small-grid paths with it)
   long long defer_grid_min = kDeferGridMin;
   // MRAFT_TICK_LIGHT (mraft_set_tick_mode): the lists of groups for the full
-  // tick (shard s at its first group + 512 s), a pair of counter sets per shard (the light
+  // tick (shard s at lite_list_begin), a pair of counter sets per shard (the light
   // launch counts into one, the fallback zeroes the other for the next tick)
   // and per shard the last fallback count, pinned (dhint + kHintLite + s)
   int32_t tick_mode = MRAFT_TICK_AUTO;

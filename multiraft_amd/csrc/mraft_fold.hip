@@ -49,22 +49,6 @@ __device__ __forceinline__ bool reply_index_ok(int prev, int n) {
   return n >= 0 && index_in_domain((int64_t)prev + n);
 }
 
-template <int P>
-__device__ __forceinline__ int quorum_rt(const int (&m)[8], int me) {
-  constexpr int h = P / 2;
-  if (h == 0) return INT32_MAX;
-  int best = INT32_MIN;
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    if (j == me) continue;
-    int c = 0;
-#pragma unroll
-    for (int q = 0; q < P; ++q) c += (q != me && m[q] >= m[j]) ? 1 : 0;
-    if (c >= h && m[j] > best) best = m[j];
-  }
-  return best;
-}
-
 #ifndef MRAFT_FOLD_GRID
 #define MRAFT_FOLD_GRID (1 << 30)  // workgroups of the reply fold (segments beyond: grid-stride)
 #endif
@@ -254,7 +238,7 @@ __device__ __forceinline__ void fold_segment(const Dev &s, const mraft_ae_result
           nxp = mv + 1;                                                  // :77
 #pragma unroll
           for (int j = 0; j < P; ++j) if (j == pr) m[j] = mv;
-          const int top = min(quorum_rt<P>(m, me), last);                // a1, :78
+          const int top = min(quorum<P>(m, me), last);                // a1, :78
           if (top > H) {
             if (lane == k) { plo = H + 1; phi = top; }
             H = top;
@@ -472,7 +456,7 @@ __device__ __forceinline__ void fold_groupw(const Dev &s, const mraft_ae_result 
           nxp = mv + 1;                                                  // :77
 #pragma unroll
           for (int j = 0; j < P; ++j) if (j == pr) m[j] = mv;
-          const int top = min(quorum_rt<P>(m, me), last);                // a1, :78
+          const int top = min(quorum<P>(m, me), last);                // a1, :78
           if (top > H) {
             if (gl == k) { plo = H + 1; phi = top; }
             H = top;

@@ -1,6 +1,9 @@
 // mraft_internal.h — the host side of the launches: the launchers each kernel
 // translation unit defines for the C-ABI implementation (mraft_abi_*.hip), under
-// the name of the file that defines them, and the helpers those launchers share.
+// the name of the file that defines them, the helpers those launchers share,
+// and the layout of each buffer a kernel indexes and the host sizes or carves
+// (the handler's HsArgs, counters and order buffer; the light tick's lists and
+// counters), stated here once for both sides.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -109,38 +112,82 @@ void launch_export(const Dev &s, const int32_t *lpeer, int32_t *commit, int32_t 
 void launch_claim_ae(const mraft_ae_args *args, int64_t n, int64_t n_log, int L, int64_t gp, int ni,
                      unsigned long long *claim, uint32_t *srcmark, uint32_t epoch, int32_t *err, uint8_t *sethd,
                      unsigned long long *total, hipStream_t st);
-// The by-reference handler's counter buffer (u64 words: [2] the published
-// deferred count, [3] the fallback's finished workgroups, then per stripe —
-// the main launch workgroup's XCD — its deferred items and its staged words,
-// one 128-B line each) and its stripes: stripe x lists its deferred items at
-// defer[x * n] (the list buffer holds kAeStripes * n) and stages at
-// stage[x * capacity / kAeStripes].
+// The by-reference handler's stripes (the main launch workgroup's XCD): stripe
+// x lists its deferred items at defer[x * n] (the list buffer holds
+// kAeStripes * n) and stages at stage[x * capacity / kAeStripes].
 #ifndef MRAFT_AE_STRIPES
 #define MRAFT_AE_STRIPES 8
 #endif
 constexpr int kAeStripes = MRAFT_AE_STRIPES;
-constexpr int kAeTotalWords = 16 + 2 * kAeStripes * 16;
-// The deferred launch's buffers and grid ("the deferred launch's fallback"):
-// per item a 16-B record (writer, arrivals, run flag, cycle counter) and a
-// reader count, nslot cycle buffers of L words, the last workgroup's L-word
-// buffer, the pinned host word with the last deferred count, and the grid the
-// host chose from it.
-struct AeDeferBufs {
-  int4 *fb;
-  unsigned long long *kin;
-  int32_t *cslot;
+// Its counter buffer (HsArgs::total, u64 words): two single words, then per
+// stripe x one 128-B line (kAeCntStripe words) at kAeCntDeferred and one at
+// kAeCntStaged, word + kAeCntStripe * x. k_claim_ae arms all but the
+// published count for each call.
+constexpr int kAeCntPublished = 2;     // the deferred count last published to the host's pinned word
+constexpr int kAeCntFbDone = 3;        // the fallback's stripes whose workgroups have all finished
+constexpr int kAeCntStripe = 16;
+constexpr int kAeCntDeferred = 16;                        // stripe x's deferred items
+constexpr int kAeCntFbStripeDone = kAeCntDeferred + 1;    // the fallback's finished workgroups of stripe x (same line)
+constexpr int kAeCntStaged = kAeCntDeferred + kAeStripes * kAeCntStripe;  // stripe x's staged words
+constexpr int kAeTotalWords = kAeCntStaged + kAeStripes * kAeCntStripe;
+
+// Every argument of the handler kernels (k_handle_set, k_handle_deferred), as
+// their one kernel argument, which the host fills (mraft_abi_msg.hip). Field
+// order and types are the kernels' argument layout.
+struct HsArgs {
+  Dev s;
+  const mraft_ae_args *args;
+  int64_t n;
+  const int32_t *ent0;  // entries in a caller buffer (launch_handle_ae_host)
+  int64_t n_ent0;
+  int32_t *stage;       // staged entries of deferred `read` items (the cycle buffer in the fallback)
+  int64_t stage_cap;    // its capacity in words
+  int64_t *soff;        // per deferred item: its staged offset, or -2 (in place)
+  const uint8_t *sethd; // per item: the size of the set it heads, else 0
+  int64_t *defer;       // the deferred items, a list of n per stripe
+  unsigned long long *total;  // the counter buffer (kAeCnt*, kAeTotalWords words)
+  const unsigned long long *claim;
+  const uint32_t *srcmark;
+  uint32_t epoch;
+  // The deferred launch's fallback (staged words past the stage capacity),
+  // per item, written by the main launch for its deferred items:
+  int4 *fb;                  // {claimant of the row it reads (its writer, fb_writer), readers of its
+                             // row already run, run flag, short-cycle readiness at the cycle's
+                             // smallest item}: one 16-B record, zeroed but the first word
+  unsigned long long *kin;   // epoch-tagged count of the deferred items that read this item's row
+  int32_t *cslot;            // per-workgroup cycle buffers, nslot x L words
   int nslot;
-  int32_t *cyc;
-  long long *hint;
-  int grid;
+  int32_t *cyc;              // the last workgroup's cycle buffer (L words)
+  long long *hint;           // pinned host words: [0] the last deferred count (the next call's grid),
+                             // [1] staged words of the last batch that exceeded the stage
+  mraft_ae_reply *rep;
+  int32_t *err;
+  mraft_ae_result *res;  // optional: each item's reply as its co-resident leader folds it
 };
-void launch_handle_ae_ref(const Dev &s, const mraft_ae_args *args, int64_t n, int ni, const unsigned long long *claim,
-                          const uint32_t *srcmark, uint32_t epoch, int32_t *err, const uint8_t *sethd, int64_t *soff,
-                          int64_t *defer, unsigned long long *total, int32_t *stage, int64_t stage_cap,
-                          const AeDeferBufs &db, mraft_ae_reply *rep, mraft_ae_result *res, hipStream_t st);
+// The fallback's `order` buffer, one allocation behind fb, cyc and cslot: n
+// records, the L-word buffer, nslot cycle buffers (ka.n, ka.s.L and ka.nslot
+// set). Returns its size in bytes and, given the buffer, points the three at
+// their parts.
+inline size_t ae_order_carve(HsArgs &ka, void *order) {
+  const size_t n = (size_t)ka.n, L = (size_t)ka.s.L;
+  if (order) {
+    ka.fb = (int4 *)order;
+    ka.cyc = (int32_t *)(ka.fb + n);
+    ka.cslot = ka.cyc + L;
+  }
+  return n * sizeof(int4) + (1 + (size_t)ka.nslot) * L * sizeof(int32_t);
+}
+// The main launch (ni messages per set at most) and the deferred launch on
+// `grid` workgroups, the host's choice from the last call's deferred count.
+void launch_handle_ae_ref(const HsArgs &ka, int ni, int grid, hipStream_t st);
 // AppendEntries with the entries in a caller buffer (claims by launch_claim).
 void launch_handle_ae_host(const Dev &s, const mraft_ae_args *args, int64_t n, const int32_t *ent, int64_t n_ent,
                            mraft_ae_reply *rep, int32_t *err, mraft_ae_result *res, hipStream_t st);
+
+// ---------------------------------------------------------------- mraft_handle_deferred.hip
+// The deferred launch alone (launch_handle_ae_ref enqueues it after the main
+// launch): k_handle_deferred, grid-stride over the deferred items.
+void launch_handle_deferred(const HsArgs &ka, int grid, hipStream_t st);
 
 // ---------------------------------------------------------------- mraft_fold.hip
 void launch_fold(const Dev &s, const mraft_ae_result *items, int64_t n, const int64_t *seg_begin,
@@ -151,25 +198,40 @@ size_t fold_scan_bytes(int64_t n, int64_t n_seg);  // scratch launch_fold needs 
 // ---------------------------------------------------------------- mraft_tick.hip
 void launch_replicate_tick(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
                            int32_t *exp_term_leader, hipStream_t st);
-// The light tick (MRAFT_TICK_LIGHT): k_tick_lite settles the
-// steady-state groups eight per wave (32 per workgroup) and lists the others,
-// per XCD: list region x = [x * lite_cap(G), ...), its count at cnt[32 x]
-// (eight counters, one 128-B line each); the fallback launch (grid
+// The light tick (MRAFT_TICK_LIGHT): k_tick_lite (mraft_tick_lite.hip)
+// settles the steady-state groups eight per wave, kLiteBlockGroups per
+// workgroup, and lists the others, per XCD: list region x =
+// [x * lite_cap(G), ...), its count at cnt[kLiteCntStride * x] (eight
+// counters, one 128-B line each); the fallback launch (k_tick_list here, grid
 // workgroups, grid-stride) runs them through the full tick, zeroes cnt_next
 // (the next light tick's counters) and writes the total to the pinned host
 // word hint. A list of G groups needs at most lite_list_words(G) words.
-inline int lite_blocks(int G) { return (G + 31) / 32; }
-inline int lite_cap(int G) { return (lite_blocks(G) + 7) / 8 * 32; }
-inline int64_t lite_list_words(int G) { return 8 * (int64_t)lite_cap(G); }
-constexpr int kLiteCntWords = 8 * 32;  // one light tick's counters
+constexpr int kLiteBlockGroups = 32;
+constexpr int kLiteCntStride = 32;
+constexpr int kLiteCntWords = 8 * kLiteCntStride;  // one light tick's counters
+constexpr int lite_blocks(int G) { return (G + kLiteBlockGroups - 1) / kLiteBlockGroups; }
+constexpr int lite_cap(int G) { return (lite_blocks(G) + 7) / 8 * kLiteBlockGroups; }
+constexpr int64_t lite_list_words(int G) { return 8 * (int64_t)lite_cap(G); }
+// One list buffer serves every tick shard: the shard s of groups
+// [g0, g0 + G_s) owns the words from lite_list_begin(g0, s), which the next
+// shard's region cannot reach: 8 * lite_cap(G_s) <= kLiteBlockGroups *
+// (lite_blocks(G_s) + 7) <= G_s + 8 * kLiteBlockGroups - 1, met at G_s = 257.
+constexpr int kLiteListSlack = 512;  // words of a shard's region beyond its groups
+static_assert(8 * kLiteBlockGroups - 1 <= kLiteListSlack && lite_list_words(257) == 257 + 8 * kLiteBlockGroups - 1,
+              "a shard's list fits its region");
+constexpr int64_t lite_list_begin(int g0, int s) { return g0 + (int64_t)kLiteListSlack * s; }
+// The buffer for G groups in at most `shards` shards.
+constexpr int64_t lite_list_alloc_words(int G, int shards) { return lite_list_begin(G, shards); }
 struct LiteBufs {
   int32_t *list;
   unsigned *cnt, *cnt_next;
   long long *hint;
   int grid;
 };
-void launch_replicate_tick_light(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
-                                 int32_t *exp_term_leader, const LiteBufs &lb, const StartIO *sio, hipStream_t st);
+// The fallback launch alone, for P >= 2 (launch_replicate_tick_light enqueues
+// it after k_tick_lite).
+void launch_tick_list(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
+                      int32_t *exp_term_leader, const LiteBufs &lb, hipStream_t st);
 // The algorithmic count's buffer (mraft_replicate_tick_count): kCountStripes
 // stripes of {reads, writes, active groups}, one 128-B line each, by
 // workgroup (one counter word per buffer took every wave's atomic in turn:
@@ -178,6 +240,12 @@ constexpr int kCountStripes = 64;
 constexpr int kCountWords = 16;
 void launch_replicate_tick_count(const Dev &s, const int32_t *lpeer, unsigned long long *counts,
                                  hipStream_t st);
+
+// ---------------------------------------------------------------- mraft_tick_lite.hip
+// The light tick's pair of launches; sio: Start at the leaders first, inside
+// k_tick_lite. With P == 1 the full tick (a lane per group already).
+void launch_replicate_tick_light(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
+                                 int32_t *exp_term_leader, const LiteBufs &lb, const StartIO *sio, hipStream_t st);
 
 // ---------------------------------------------------------------- mraft_elect.hip
 void launch_election_rounds(const Dev &s, const uint8_t *cand, int R, int32_t *gflags,

@@ -2,8 +2,9 @@
 // a lane (or a wave) per item: Make, the slot claims, the AppendEntries gather,
 // Start, the applier, snapshots, RequestVote and its tally, persistence and
 // GetState (the per-message entry points of include/mraft.h).
-// The AppendEntries handler lives in mraft_handle_ae.hip, the reply fold in
-// mraft_fold.hip, the fused co-resident tick in mraft_tick.hip.
+// The AppendEntries handler lives in mraft_handle_ae.hip and
+// mraft_handle_deferred.hip, the reply fold in mraft_fold.hip, the fused
+// co-resident tick in mraft_tick.hip and mraft_tick_lite.hip.
 #include "mraft_device.h"
 #include "mraft_internal.h"
 #include "mraft_rules.h"

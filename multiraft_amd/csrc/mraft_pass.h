@@ -1,6 +1,6 @@
 // mraft_pass.h — the streaming entry-merge pass shared by the fused tick
 // (mraft_tick.hip) and the message-level HandleAppendEntries
-// (mraft_handle_ae.hip): raft_append_entry.go:146-155's compare-then-truncate-
+// (mraft_handle_ae.h): raft_append_entry.go:146-155's compare-then-truncate-
 // and-append over one source of entries (`src`: the leader's log row, or a
 // network batch) into up to NI follower rows of `log`, 256 entries per wave
 // iteration, first mismatch by ballot, and — for the tick — the exact a1

@@ -1,6 +1,7 @@
 // mraft_rules.h — the item-level rules more than one kernel applies, each
 // stated once: the Index domain, the reply segments' prologue, the claim word,
-// Start, the applier's message and the GetState word. Every helper inlines to
+// Start, the applier's message, the quorum order statistic and the GetState
+// word with the tick's export of it. Every helper inlines to
 // the arithmetic it names (the hot kernels' code is the same with or without).
 #pragma once
 #include "../../include/mraft.h"
@@ -125,9 +126,44 @@ __device__ __forceinline__ ApplyMsg apply_slot(const Dev &s, int64_t i, int hs, 
   return m;
 }
 
+// ---------------------------------------------------------------- quorum
+// advanceCommitIndexForLeader's order statistic (raft_append_entry.go:91-98)
+// over the first P words of m: the h-th largest (h = P/2) of matchIndex[j != me],
+// the largest i for which #{j != me : matchIndex[j] >= i} + 1 > P/2. With no
+// peer (h = 0) every Index has its quorum.
+template <int P, int N>
+__device__ __forceinline__ int quorum(const int (&m)[N], int me) {
+  static_assert(P <= N, "m holds a word per peer");
+  constexpr int h = P / 2;
+  if (h == 0) return INT32_MAX;
+  int best = INT32_MIN;
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    if (j == me) continue;
+    int c = 0;
+#pragma unroll
+    for (int q = 0; q < P; ++q) c += (q != me && m[q] >= m[j]) ? 1 : 0;
+    if (c >= h && m[j] > best) best = m[j];
+  }
+  return best;
+}
+
+// ---------------------------------------------------------------- GetState
 // GetState (raft.go:237-246) in one word: currentTerm << 1 | isLeader.
 __device__ __forceinline__ int32_t term_leader_word(int term, int role) {
   return (int32_t)(((uint32_t)term << 1) | (role == kLeader ? 1u : 0u));
 }
+
+// GetState of the group's exported replica, fused into the tick
+// (mraft_replicate_tick_export): commit and the GetState word.
+struct Export {
+  int32_t *commit, *term_leader;
+  __device__ __forceinline__ void put(int g, int c, int t, int role) const {
+    if (commit) {
+      commit[g] = c;
+      term_leader[g] = term_leader_word(t, role);
+    }
+  }
+};
 
 }  // namespace mraft

@@ -198,7 +198,7 @@ def main():
     for m in ("aligned", "reference", "ordered"):
         out["cases"].append([m + "_low", message_case(m, shift=False, seed=407)])
     malformed_case()
-    for fn in ("mraft_debug_bounds_kernels", "mraft_debug_bounds_tick"):
+    for fn in ("mraft_debug_bounds_kernels", "mraft_debug_bounds_deferred", "mraft_debug_bounds_tick"):
         f = getattr(lib, fn)
         f.restype = __import__("ctypes").c_longlong
         f.argtypes = [__import__("ctypes").c_int]

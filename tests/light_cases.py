@@ -1,5 +1,5 @@
 """States built group by group for the light tick (MRAFT_TICK_LIGHT,
-include/mraft.h; k_tick_lite in multiraft_amd/csrc/mraft_tick.hip). Test
+include/mraft.h; k_tick_lite in multiraft_amd/csrc/mraft_tick_lite.hip). Test
 infrastructure, numpy only.
 
 Nothing here runs a workload forward: every group's leader log, every
@@ -32,7 +32,7 @@ from oracle_lib import terms_sorted_exact
 from multiraft_amd._abi import CANDIDATE, FOLLOWER, ITEM_BAD_SLOT, ITEM_LOG_FULL, LEADER
 from multiraft_amd.engine import new_state
 
-LITE_SPAN = 64  # kLiteSpan in multiraft_amd/csrc/mraft_tick.hip: the longest run the light launch copies
+LITE_SPAN = 64  # kLiteSpan in multiraft_amd/csrc/mraft_tick_lite.hip: the longest run the light launch copies
 CAPACITIES = (37, 64, 99, 256)
 PEERS = (2, 3, 4, 5, 6, 7, 8)
 FAMILIES = ("A", "B", "C", "D", "E", "F")

@@ -42,7 +42,7 @@ from multiraft_amd._abi import FOLLOWER, LEADER
 from multiraft_amd.engine import entry_positions, new_state
 
 CHUNK = 256   # entries per chunk of the pass (mraft_pass.h: CW = 64 * EPL, EPL = 4; pass_chunk<1>: 256 * V)
-LINE = 32     # entries per 128-B line: MRAFT_TICK_ALIGN (mraft_tick.hip), handle_one's `& 31`
+LINE = 32     # entries per 128-B line: MRAFT_TICK_ALIGN (mraft_tick.hip), handle_one's `& 31` (mraft_handle_ae.h)
 WAVE = 64     # lanes; the ConflictIndex probe reads one term per lane
 TB = 5000     # term of a group's leader dummy
 POISON = 7777

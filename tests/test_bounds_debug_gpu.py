@@ -29,4 +29,5 @@ def test_no_ring_offset_out_of_range_gpu():
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert len(out["cases"]) >= 12 and all(c[-1] > 0 for c in out["cases"]), out["cases"]
-    assert out["violations"] == {"mraft_debug_bounds_kernels": 0, "mraft_debug_bounds_tick": 0}, out
+    assert out["violations"] == {"mraft_debug_bounds_kernels": 0, "mraft_debug_bounds_deferred": 0,
+                                 "mraft_debug_bounds_tick": 0}, out

@@ -1,7 +1,7 @@
 """The message-level AppendEntries handler with no host round trip (VERDICT r4
 item 1): mraft_handle_append_entries[_ex] by reference enqueues its three
 launches and returns, whatever the batch; items that must run after others
-are ordered on the device (include/mraft.h, mraft_handle_ae.hip "a4").
+are ordered on the device (include/mraft.h, mraft_handle_ae.h "a4").
 
 * K message steps (gather -> HandleAppendEntries -> reply fold,
   src/raft/raft_append_entry.go:20-162) enqueued back to back on one engine

@@ -4,7 +4,8 @@
 # Each argument is  tag[@SRCDIR]=DEFINES  e.g.  "w6=-DMRAFT_TICK_MINW=6 -DMRAFT_TICK_CMP_EPL=2"
 # or "head@/tmp/head/multiraft_amd/csrc=" (another source tree, e.g. git archive HEAD).
 # The sources and flags are the Makefile's (of the tree being built).
-# TICK_ONLY=1: recompile only mraft_tick.hip per variant (the rest from build/).
+# TICK_ONLY=1: recompile only mraft_tick.hip per variant (the rest from build/;
+# every MRAFT_TICK_* knob is in that unit, the light kernel of mraft_tick_lite.hip has none).
 set -e
 cd "$(dirname "$0")/../multiraft_amd/csrc"
 OUT=$(cd ../../tools && pwd)/variants
