@@ -449,7 +449,8 @@ int mraft_process_append_replies(mraft_engine *h, const mraft_ae_result *items,
  * its message (a4 / HandleInstallSnapshot) and the leader folds the replies
  * in peer order (a2 + a1 / processInstallSnapshotReply). Equivalent to the
  * sequence gather -> handle -> process on the same state.
- * group_flags (optional, [G]) gets MRAFT_G_* bits. */
+ * group_flags (optional, [G]) gets MRAFT_G_* bits. Under a reachability mask
+ * (mraft_set_reachable) only the messages between connected replicas pass. */
 int mraft_replicate_tick(mraft_engine *h, const int32_t *leader_peer,
                          int32_t *group_flags, int32_t where);
 
@@ -651,7 +652,8 @@ int mraft_process_vote_replies(mraft_engine *h, const mraft_rv_result *items,
  * delivered (HandleRequestVote, :54-77), voter by voter in candidate order;
  * then every candidate tallies its replies in voter order (:22-47; on a
  * majority: Leader, matchIndex[*]=0, nextIndex[*]=lastIndex+1). No message
- * is lost. group_flags (optional, [G]) gets MRAFT_G_ELECTED /
+ * is lost (under a reachability mask, mraft_set_reachable, those between two
+ * connected replicas). group_flags (optional, [G]) gets MRAFT_G_ELECTED /
  * MRAFT_G_STEPPED_DOWN. P <= 8 (one mask byte per group and round). */
 int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask,
                           int32_t rounds, int32_t *group_flags, int32_t where);
@@ -661,7 +663,7 @@ int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask,
 /* Optional capabilities of this build, a bitmask (the ABI version says which
  * structs and entry points exist; a feature bit says a later addition that
  * changed none of them is present). */
-enum { MRAFT_FEATURE_TIMERS = 1 };
+enum { MRAFT_FEATURE_TIMERS = 1, MRAFT_FEATURE_REACH = 2 };
 int32_t mraft_features(void);
 
 /* Timer state: per replica slot the absolute time, in caller-defined clock
@@ -793,6 +795,50 @@ enum { MRAFT_CLOCK_SEND_ALL = 1 };
 int mraft_clock_step(mraft_engine *h, int32_t now, uint32_t flags, uint8_t *cand_mask,
                      int32_t *leader_peer, int32_t *election_flags, int32_t *group_flags,
                      int32_t *commit, int32_t *term_leader, int32_t where);
+
+/* ---- reachability (MRAFT_FEATURE_REACH; config.go connect()/disconnect()) -- */
+
+/* config.go connect()/disconnect() for co-resident groups. reach[g], one byte per
+ * group: bit p set = replica p of group g is connected. A message from replica a
+ * to replica b, and its reply, pass iff bits a and b are both set (one connected
+ * set per group, every other replica isolated: exactly what config.go can
+ * express). Bits at and above P are ignored. NULL: everyone connected, the
+ * behaviour before this call existed. The engine keeps its own copy (G bytes);
+ * the call is ordered on the engine stream like any other. MRAFT_E_NOSTATE
+ * without bound state.
+ *
+ * While a mask is set the co-resident calls honour it; the message-level calls
+ * do not (there the host chooses the deliveries).
+ *  - The tick (mraft_replicate_tick, _export, mraft_start_and_tick, step D of
+ *    mraft_clock_step): the leader's own a3 runs for every follower, so
+ *    MRAFT_G_ERROR (prev > last at any follower) and MRAFT_G_NEED_SNAPSHOT are
+ *    as without a mask. Follower p receives its AppendEntries / InstallSnapshot
+ *    iff bit leader_peer[g] and bit p are set; a follower that receives nothing
+ *    is untouched (term, role, log, commit, persist bit), and so are its
+ *    nextIndex / matchIndex words at the leader. The leader folds the replies
+ *    that exist, in peer order; a1's quorum is still taken over all P
+ *    matchIndex words. A leader whose own bit is clear delivers nothing:
+ *    MRAFT_G_ACTIVE plus the a3 flags, no state change. SNAPSHOT_INSTALLED,
+ *    FOLLOWER_PANIC, LOG_FULL and FOLLOWER_COMMIT cover delivered messages
+ *    only. Start inside mraft_start_and_tick is local. Tick modes and shards
+ *    compose with the mask (light mode settles fully connected groups and
+ *    sends every other group to the full tick).
+ *    mraft_replicate_tick_count returns MRAFT_E_INVAL while a mask is set.
+ *  - The election round (mraft_election_rounds, step B of mraft_clock_step): a
+ *    timed-out non-leader runs StartElection whether it is connected or not;
+ *    candidate c's RequestVote reaches voter v iff both bits are set, in
+ *    candidate order; c tallies those voters' replies in voter order against
+ *    the unchanged majority (> P/2 of all P). A candidate that is cut off ends
+ *    the round as Candidate with grantedVotes = 1; a replica that handles no
+ *    RequestVote gets no persist mark for one.
+ *  - mraft_clock_step: A and C are local (timeouts; the highest-term Leader is
+ *    still the one sender, connected or not). In B "granted another replica"
+ *    follows the deliveries. E resets a non-sender only when its bit and the
+ *    sender's are both set. */
+int mraft_set_reachable(mraft_engine *h, const uint8_t *reach, int32_t where);
+/* 1 and the current mask in out[G] when one is set, 0 (out untouched) when
+ * none; negative on error. */
+int mraft_get_reachable(mraft_engine *h, uint8_t *out, int32_t where);
 
 /* ---- persistence (raft.go:205-235, persister.go) ------------------------- */
 

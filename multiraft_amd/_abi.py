@@ -38,6 +38,7 @@ FANIN_OVERLAP = 1
 FANIN_ORDERED = 2
 COMM_ID_BYTES = 128
 FEATURE_TIMERS = 1  # mraft_features
+FEATURE_REACH = 2   # mraft_set_reachable / mraft_get_reachable
 (NOTE_AE_HANDLED, NOTE_IS_HANDLED, NOTE_RV_HANDLED, NOTE_AE_FOLDED, NOTE_IS_FOLDED,
  NOTE_RV_FOLDED) = range(6)  # mraft_timers_note kinds
 CLOCK_SEND_ALL = 1
@@ -117,7 +118,7 @@ ABI_SYMBOLS = (
     "mraft_set_tick_mode", "mraft_get_tick_mode", "mraft_tick_light_fallbacks", "mraft_start_and_tick",
     "mraft_features", "mraft_timer_draw", "mraft_timers_enable", "mraft_timers_disable",
     "mraft_timers_load", "mraft_timers_store", "mraft_timers_arm", "mraft_ticker",
-    "mraft_timers_note", "mraft_clock_step",
+    "mraft_timers_note", "mraft_clock_step", "mraft_set_reachable", "mraft_get_reachable",
 )
 SYNTH_SYMBOLS = ("mraft_synth_tick_state", "mraft_synth_fold_batch", "mraft_synth_election_state")
 
@@ -187,6 +188,8 @@ _SIGS = {
     "mraft_ticker": (ctypes.c_int, [_vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i32]),
     "mraft_timers_note": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32]),
     "mraft_clock_step": (ctypes.c_int, [_vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "mraft_set_reachable": (ctypes.c_int, [_vp, _vp, _i32]),
+    "mraft_get_reachable": (ctypes.c_int, [_vp, _vp, _i32]),
 }
 _SYNTH_SIGS = {
     "mraft_synth_tick_state": (ctypes.c_int, [ctypes.c_uint64, _i32, _i32, _i32, _i32, _i32,

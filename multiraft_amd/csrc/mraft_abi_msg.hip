@@ -285,7 +285,7 @@ int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask, int32_t rou
   const uint8_t *m = sg.in(cand_mask, (size_t)rounds * h->G);
   int32_t *gf = sg.out(group_flags, h->G);
   TRY(sg.status());
-  mraft::launch_election_rounds(dev_of(h), m, rounds, gf, h->stream);
+  mraft::launch_election_rounds(dev_of(h), m, rounds, gf, h->reach, h->stream);
   return sg.finish();
 }
 

@@ -44,11 +44,13 @@ void tick_range(mraft_engine *h, const mraft::Dev &d, int s, int32_t g0, const i
                 int32_t *ec, int32_t *et, hipStream_t st, const mraft::StartIO *sio = nullptr) {
   const bool light = h->P >= 2 && (h->tick_mode == MRAFT_TICK_LIGHT ||
                                    (h->tick_mode == MRAFT_TICK_AUTO && auto_light(h, s, d.G)));
+  // the reachability mask (mraft_set_reachable), when one is set: the range's bytes
+  const uint8_t *reach = h->reach ? h->reach + g0 : nullptr;
   mraft::StartIO so{};
   if (sio) so = {sio->counts + g0, sio->oi + g0, sio->ot + g0, sio->ol + g0, sio->err + g0};
   if (!light) {
     if (sio) mraft::launch_start_groups(d, lp + g0, so, st);
-    mraft::launch_replicate_tick(d, lp + g0, off(gf, g0), off(ec, g0), off(et, g0), st);
+    mraft::launch_replicate_tick(d, lp + g0, off(gf, g0), off(ec, g0), off(et, g0), reach, st);
     return;
   }
   mraft::LiteBufs lb;
@@ -63,7 +65,8 @@ void tick_range(mraft_engine *h, const mraft::Dev &d, int s, int32_t g0, const i
   // one wave per SIMD slot, grid-stride
   const long long gr = prev < 0 ? kLiteGridUnknown : std::max(kLiteGridMin, 2 * prev);
   lb.grid = (int)std::max(1ll, std::min(gr, (long long)d.G));
-  mraft::launch_replicate_tick_light(d, lp + g0, off(gf, g0), off(ec, g0), off(et, g0), lb, sio ? &so : nullptr, st);
+  mraft::launch_replicate_tick_light(d, lp + g0, off(gf, g0), off(ec, g0), off(et, g0), lb, sio ? &so : nullptr,
+                                     reach, st);
 }
 
 }  // namespace
@@ -138,6 +141,8 @@ int mraft_replicate_tick_count(mraft_engine *h, const int32_t *leader_peer, int6
                                int32_t where) {
   TRY(enter(h));
   if (!leader_peer || !out_words) return fail(MRAFT_E_INVAL, "null argument");
+  if (h->reach)
+    return fail(MRAFT_E_INVAL, "the word count is defined for the full network only: a reachability mask is set");
   Stage sg(h, where);
   const int32_t *lp = sg.in(leader_peer, h->G);
   TRY(sg.status());

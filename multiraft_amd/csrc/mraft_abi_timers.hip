@@ -173,14 +173,15 @@ int mraft_clock_step(mraft_engine *h, int32_t now, uint32_t flags, uint8_t *cand
   TRY(scratch(h, kScrClockTg, G, &tg));
   int32_t *lp = need[0], *gf = need[1];
   const mraft::TimerDev t = timers_of(h);
-  // A-C: ticker, one election round, the sender
-  mraft::launch_clock_round(dev_of(h), t, now, flags, cm, lp, tg, ef, h->stream);
+  // A-C: ticker, one election round, the sender (every launch of the step
+  // under the reachability mask, when one is set)
+  mraft::launch_clock_round(dev_of(h), t, now, flags, cm, lp, tg, ef, h->reach, h->stream);
   // D: the tick, under the handle's mode and shards
   TRY(launch_tick(h, lp, gf, need[2], need[3]));
   // E: the tick's resets, on the engine stream after every shard (a
   // device-side wait)
   TRY(join_shards(h));
-  mraft::launch_clock_resets(dev_of(h), t, now, gf, lp, tg, h->stream);
+  mraft::launch_clock_resets(dev_of(h), t, now, gf, lp, tg, h->reach, h->stream);
   return sg.finish();
 }
 

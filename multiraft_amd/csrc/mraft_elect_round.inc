@@ -7,7 +7,13 @@
 //   P (constexpr), p, pb = 1 << p, act, seg, m (the round's timeout mask),
 //   upm (isLogUpToDate bits), the replica's registers term, vb, role, votes,
 //   the accumulators fl, became, pd, and the __shared__ arrays lds_cx, lds_gm,
-//   lds_rt, lds_rc (256 entries each).
+//   lds_rt, lds_rc (256 entries each);
+//   REACH (constexpr bool) and rmask, the group's reachability word
+//   (mraft_set_reachable, bit q: replica q is connected). The unmasked kernels
+//   say REACH = false with rmask the constant all-ones, and every test of it
+//   compiles away. Under a mask candidate c's RequestVote reaches voter v, and
+//   v's reply reaches c, iff both their bits are set; timeouts and
+//   StartElection are local and happen either way.
 // It leaves in scope: isc (this lane ran StartElection), gm (bit c: this voter
 // granted candidate c's RequestVote; a candidate's own bit is set by its
 // delivery to itself, so "granted another replica" is (gm & ~pb) != 0).
@@ -41,7 +47,10 @@
     // The segment's candidate mask (ascending peer order is the delivery order).
     const unsigned long long cb = __ballot(isc);
     const int cm = (int)((cb >> seg) & 0xffull);
-    pd |= (int)(act && (cm & ~(1 << p)) != 0);                         // :57, every RV this voter handles
+    // the candidates whose RequestVote this replica receives
+    const int conn = REACH ? (rmask >> p) & 1 : 1;
+    const int cmv = REACH ? (conn ? cm & rmask : 0) : cm;
+    pd |= (int)(act && (cmv & ~(1 << p)) != 0);                        // :57, every RV this voter handles
     // The segment's candidates ranked in peer order: rank k's args.Term and
     // peer index staged through LDS once per round and held in registers, so
     // the delivery loop has no LDS round trip per candidate and a compile-time
@@ -69,8 +78,12 @@
 #pragma unroll
       for (int k = 0; k < P; ++k) {
         if (!__ballot(k < ncand)) break;
-        const int cb = (int)((rcs >> (8 * k)) & 0xffull);
-        const int cat = rt[k];
+        int cb = (int)((rcs >> (8 * k)) & 0xffull);
+        int cat = rt[k];
+        if (REACH && !(cb & cmv)) {  // not delivered: the slot past the candidates, which changes nothing
+          cb = 0;
+          cat = INT32_MIN;
+        }
         pmx = cb <= pb ? max(pmx, cat) : pmx;                          // c <= p
         const bool gt = cat > term;                                    // :63-66
         const bool ge = cat >= term;                                   // :59-62 (stale: no change)
@@ -97,14 +110,22 @@
     // grant that makes a majority (:32-38) or stepping down at the first
     // refusal whose reply.Term exceeds args.Term (:42-45), so the fold is
     // closed-form: whichever of the two positions comes first in voter order.
+    // Under a mask the same holds inside the connected set: a connected
+    // candidate receives every other connected candidate's RequestVote, as
+    // every connected voter does, so pmx on its lane is the pmx of each voter
+    // whose reply it gets; its grants (mine) can only come from voters its
+    // RequestVote reached, its refusals (smask) are restricted to them, and
+    // the majority stays P/2 grants of all P. A candidate that is cut off
+    // hears no reply: it skips the tally and stays Candidate with its own vote.
     {
-      const bool ok0 = isc && term == at && role == kCandidate;
+      bool ok0 = isc && term == at && role == kCandidate;
+      if (REACH) ok0 = ok0 && conn;
       const int om = ((1 << P) - 1) & ~(1 << p);
       int gt = 0, tv = 0;
 #pragma unroll
       for (int v = 0; v < P; ++v) gt |= (int)((cx[v]) > at) << v;
       // reply.Term = max(voter's own term, pmx) > at: every refusal when pmx > at.
-      const int smask = om & ~mine & (pmx > at ? om : gt);
+      const int smask = om & ~mine & (pmx > at ? om : gt) & (REACH ? rmask : -1);
       int mm = mine & om;
 #pragma unroll
       for (int k = 1; k < (P / 2 > 1 ? P / 2 : 1); ++k) mm &= mm - 1;  // the (P/2)-th grant

@@ -136,6 +136,10 @@ struct mraft_engine {
   // configuration they were armed under
   int32_t *tm_ed = nullptr, *tm_hd = nullptr;
   mraft_timer_config tcfg{};
+  // Reachability (mraft_set_reachable): the engine's copy of the mask, one
+  // byte per group, or null when none is set (everyone connected). While it is
+  // set the co-resident calls launch their *_reach kernels with it.
+  uint8_t *reach = nullptr;
   void *scratch_ptr[kScrSlots] = {};
   size_t scratch_cap[kScrSlots] = {};
 };

@@ -235,7 +235,7 @@ void teardown(mraft_engine *h) {
     for (void *p : h->scratch_ptr)
       if (p) (void)hipFreeAsync(p, h->stream);
     for (void *p : {(void *)h->claim, (void *)h->srcmark, (void *)h->ae_total, (void *)h->lite_list,
-                    (void *)h->lite_cnt, (void *)h->tm_ed, (void *)h->tm_hd})
+                    (void *)h->lite_cnt, (void *)h->tm_ed, (void *)h->tm_hd, (void *)h->reach})
       if (p) (void)hipFreeAsync(p, h->stream);
     (void)hipStreamSynchronize(h->stream);
   }
@@ -383,6 +383,39 @@ int mraft_bind_state(mraft_engine *h, const mraft_soa *d) {
   h->dev = *d;
   h->bound = true;
   return MRAFT_OK;
+}
+
+// ---------------------------------------------------------------- reachability
+
+int mraft_set_reachable(mraft_engine *h, const uint8_t *reach, int32_t where) {
+  TRY(enter(h));
+  uint8_t *fresh = nullptr;
+  if (reach) {
+    // A new buffer per call: the handle sees it only after the allocation and
+    // the copy were enqueued without error; the launches already enqueued keep
+    // the old one, which is freed in stream order behind them.
+    TRY(alloc_async(h, &fresh, (size_t)h->G, "reachability mask"));
+    const hipError_t e = hipMemcpyAsync(fresh, reach, (size_t)h->G,
+                                        where == MRAFT_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream);
+    const hipError_t e2 = e == hipSuccess && where == MRAFT_HOST ? hipStreamSynchronize(h->stream) : e;
+    if (e2 != hipSuccess) {
+      (void)hipFreeAsync(fresh, h->stream);
+      return fail(MRAFT_E_HIP, "copying the reachability mask failed: %s", hipGetErrorString(e2));
+    }
+  }
+  if (h->reach) (void)hipFreeAsync(h->reach, h->stream);
+  h->reach = fresh;
+  return MRAFT_OK;
+}
+
+int mraft_get_reachable(mraft_engine *h, uint8_t *out, int32_t where) {
+  TRY(enter(h));
+  if (!h->reach) return 0;
+  if (!out) return fail(MRAFT_E_INVAL, "out is null");
+  HIP_TRY(hipMemcpyAsync(out, h->reach, (size_t)h->G,
+                         where == MRAFT_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+  TRY(finish_copies(h, where));
+  return 1;
 }
 
 // ---------------------------------------------------------------- queues

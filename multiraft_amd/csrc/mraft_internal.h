@@ -196,8 +196,12 @@ void launch_fold(const Dev &s, const mraft_ae_result *items, int64_t n, const in
 size_t fold_scan_bytes(int64_t n, int64_t n_seg);  // scratch launch_fold needs (a1 scan list, long segments)
 
 // ---------------------------------------------------------------- mraft_tick.hip
+// `reach` (here and in every launcher below that takes it): the groups'
+// reachability bytes (mraft_set_reachable), or null when no mask is set. Null
+// launches the kernels as they are without the feature; a mask launches their
+// *_reach counterparts, which compile the same bodies with the mask's tests.
 void launch_replicate_tick(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
-                           int32_t *exp_term_leader, hipStream_t st);
+                           int32_t *exp_term_leader, const uint8_t *reach, hipStream_t st);
 // The light tick (MRAFT_TICK_LIGHT): k_tick_lite (mraft_tick_lite.hip)
 // settles the steady-state groups eight per wave, kLiteBlockGroups per
 // workgroup, and lists the others, per XCD: list region x =
@@ -231,7 +235,7 @@ struct LiteBufs {
 // The fallback launch alone, for P >= 2 (launch_replicate_tick_light enqueues
 // it after k_tick_lite).
 void launch_tick_list(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
-                      int32_t *exp_term_leader, const LiteBufs &lb, hipStream_t st);
+                      int32_t *exp_term_leader, const LiteBufs &lb, const uint8_t *reach, hipStream_t st);
 // The algorithmic count's buffer (mraft_replicate_tick_count): kCountStripes
 // stripes of {reads, writes, active groups}, one 128-B line each, by
 // workgroup (one counter word per buffer took every wave's atomic in turn:
@@ -245,11 +249,17 @@ void launch_replicate_tick_count(const Dev &s, const int32_t *lpeer, unsigned lo
 // The light tick's pair of launches; sio: Start at the leaders first, inside
 // k_tick_lite. With P == 1 the full tick (a lane per group already).
 void launch_replicate_tick_light(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
-                                 int32_t *exp_term_leader, const LiteBufs &lb, const StartIO *sio, hipStream_t st);
+                                 int32_t *exp_term_leader, const LiteBufs &lb, const StartIO *sio,
+                                 const uint8_t *reach, hipStream_t st);
 
 // ---------------------------------------------------------------- mraft_elect.hip
-void launch_election_rounds(const Dev &s, const uint8_t *cand, int R, int32_t *gflags,
+void launch_election_rounds(const Dev &s, const uint8_t *cand, int R, int32_t *gflags, const uint8_t *reach,
                             hipStream_t st);
+
+// ---------------------------------------------------------------- mraft_elect_reach.hip
+// The storm under a mask (reach non-null); launch_election_rounds calls it.
+void launch_election_rounds_reach(const Dev &s, const uint8_t *cand, int R, int32_t *gflags, const uint8_t *reach,
+                                  hipStream_t st);
 
 // ---------------------------------------------------------------- mraft_clock.hip
 // Timers (include/mraft.h "timers"): the two deadline arrays of a handle with
@@ -272,8 +282,8 @@ void launch_timers_note(const TimerDev &t, int kind, const void *records, const 
 // mraft_clock_step A-C (ticker, one election round, the sender; lpeer and tg,
 // the sender's term, are required) and E (the tick's resets).
 void launch_clock_round(const Dev &s, const TimerDev &t, int32_t now, uint32_t flags, uint8_t *cand,
-                        int32_t *lpeer, int32_t *tg, int32_t *eflags, hipStream_t st);
+                        int32_t *lpeer, int32_t *tg, int32_t *eflags, const uint8_t *reach, hipStream_t st);
 void launch_clock_resets(const Dev &s, const TimerDev &t, int32_t now, const int32_t *gflags,
-                         const int32_t *lpeer, const int32_t *tg, hipStream_t st);
+                         const int32_t *lpeer, const int32_t *tg, const uint8_t *reach, hipStream_t st);
 
 }  // namespace mraft

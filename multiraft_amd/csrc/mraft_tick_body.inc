@@ -5,12 +5,17 @@
 // form of this body compiled differently) and by k_tick_list (the light
 // tick's fallback: the groups of a device list, grid-stride). Expects P, COUNT,
 // NI, lane, g, s (Dev, the kernel's first argument: reload_dev), leader_peer,
-// gflags, counts, ex in scope and TICK_EXIT defined (return / continue).
+// gflags, counts, ex in scope and TICK_EXIT defined (return / continue); and
+// REACH (constexpr bool) with reach, the groups' reachability bytes
+// (mraft_set_reachable): the unmasked kernels say REACH = false, which makes
+// the group's reachability word the constant all-ones and every test of it
+// compile away.
   const int L = s.L;
   TICK_STAMP(0);
 
   // ------------------------------------------------------------ header
   const int lp = uni(leader_peer[g]);
+  const int rmask = REACH ? uni((int)reach[g]) : -1;  // bit p: replica p is connected
   if (lp < 0 || lp >= P) {
     if (!COUNT && lane == 0) {
       if (gflags) gflags[g] = lp >= P ? MRAFT_G_ERROR : 0;
@@ -71,6 +76,11 @@
     TICK_EXIT;
   }
   int flags = MRAFT_G_ACTIVE | (snap_m ? MRAFT_G_NEED_SNAPSHOT : 0);
+  // The a3 outcome above is the leader's own; from here on a follower whose
+  // message is not delivered (its bit or the leader's clear) holds no item:
+  // nothing of it is read, written or folded.
+  // (lanes >= NI hold no item already; their p is masked into the byte)
+  if (REACH && !(((rmask >> lp) & 1) && ((rmask >> (p & 7)) & 1))) icls = IC_NONE;
   const int probe_last = uni(s.log[lrow + ring(last + lb, L)]);  // speculative a1 probe
   int prev_term = 0, ft = 0;
   if (icls == IC_GO) {

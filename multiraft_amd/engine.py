@@ -509,6 +509,27 @@ class Engine:
                                        *(ptr(out.get(n)) for n in names), where), "mraft_clock_step")
         return out
 
+    # ---- reachability (config.go connect / disconnect) ---------------------
+    def set_reachable(self, mask, where: int = HOST):
+        """config.go's connect()/disconnect() for the co-resident calls
+        (mraft_set_reachable): mask[g] is a byte whose bit p says replica p of
+        group g is connected; a message and its reply pass iff both ends'
+        bits are set. None: everyone connected again. The tick, the election
+        round and the clock step honour it; the message-level calls do not."""
+        if mask is not None and where == HOST:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (self.G,):
+                raise ValueError(f"reachability mask of shape {mask.shape}, need ({self.G},)")
+        _ck(self._lib.mraft_set_reachable(self._h, ptr(mask), where), "mraft_set_reachable")
+
+    def get_reachable(self):
+        """The mask in force as a uint8 host array [G], or None when none is set."""
+        out = np.zeros(self.G, np.uint8)
+        rc = self._lib.mraft_get_reachable(self._h, ptr(out), HOST)
+        if rc < 0:
+            _ck(rc, "mraft_get_reachable")
+        return out if rc == 1 else None
+
     # ---- persistence (raft.go:205-235) ------------------------------------
     def collect_persist(self):
         """persist_dirty of every slot (MRAFT_PERSIST_* bits), cleared on read."""
