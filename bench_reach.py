@@ -7,7 +7,7 @@ steady state = the steps after the synthetic backlog has drained). Three
 variants alternate on fresh copies of the same state, `--repeats` times:
 
   none     no mask set: the kernels as they are without the feature;
-  full     a mask with every bit set: the *_reach kernels, every group connected;
+  full     a mask with every bit set: the masked kernels, every group connected;
   cut1pct  the same with one follower cut off in 1 % of the groups.
 
 With --parent-root DIR (a built checkout of the parent commit) the variant

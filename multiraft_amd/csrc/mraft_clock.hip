@@ -15,10 +15,11 @@
 // more: the compiler's resource remarks give every kernel 8 waves per SIMD
 // with no scratch. k_clock_round<P> takes 35 (P = 1) to 64 (P = 8) VGPRs,
 // the last exactly the 64 that 8 waves per SIMD leave each, and 2,560 B of
-// LDS per workgroup (DESIGN.md §8d records the figures). Their counterparts
-// under a reachability mask (k_clock_round_reach, k_clock_resets_reach;
-// DESIGN.md §8e) hold one more word per lane: k_clock_round_reach<8> takes 66
-// VGPRs, which leaves 7 waves per SIMD; P <= 7 keeps 8.
+// LDS per workgroup (DESIGN.md §8d records the figures). Instantiated with
+// the reachability pack (k_clock_round<P, uint8_t>, k_clock_resets<uint8_t>;
+// mraft_device.h) they hold one more word per lane:
+// k_clock_round<8, uint8_t> takes 66 VGPRs, which leaves 7 waves per SIMD;
+// P <= 7 keeps 8.
 #include "mraft_device.h"
 #include "mraft_internal.h"
 #include "mraft_timer_draw.h"
@@ -154,59 +155,125 @@ __global__ __launch_bounds__(256) void k_timers_note(TimerDev t, int kind, const
 // body are k_election_rounds' (mraft_elect.hip); this kernel adds the two
 // deadlines per lane, the per-voter grant (gm, left in scope by the round
 // body) and the sender's choice by segment shuffles.
-template <int P>
+// Under the reachability pack (mraft_device.h) A (timeouts) and C (the sender)
+// are local and take no notice of the mask; B's round does
+// (mraft_elect_round.inc), and the reset of a voter that "granted another
+// replica" follows the deliveries through gm.
+template <int P, class... M>
 __global__ __launch_bounds__(256) void k_clock_round(Dev s, TimerDev t, int now, unsigned flags,
                                                      uint8_t *__restrict__ cand, int32_t *__restrict__ lpeer,
-                                                     int32_t *__restrict__ tg, int32_t *__restrict__ gflags) {
-  constexpr bool REACH = false;  // no reachability mask: rmask is the constant all-ones
-  constexpr const uint8_t *reach = nullptr;
-#include "mraft_clock_round_kernel.inc"
-}
+                                                     int32_t *__restrict__ tg, int32_t *__restrict__ gflags,
+                                                     const M *__restrict__... reach) {
+  constexpr bool REACH = reach_given<M...>();  // false: rmask is the constant all-ones
+  const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int g = tid >> 3, p = tid & 7;
+  const bool grp = g < s.G;  // uniform over the segment
+  const bool act = grp && p < P;
+  const int rmask = grp ? reach_byte(g, reach...) : -1;  // bit q: replica q is connected
+  const long long sl = (long long)g * P + p;
+  int term = 0, voted = -1, role = kFollower, votes = 0, last = 0, lterm = 0;
+  int ed = INT32_MAX, hd = INT32_MAX;
+  if (act) {
+    term = s.term[sl];
+    voted = s.voted[sl];
+    role = s.role[sl];
+    votes = s.votes[sl];
+    last = s.last[sl];
+    lterm = term_at(s, sl, s.dummy[sl], s.head[sl], last);             // lastEntry, raft_log.go:50-53
+    ed = t.ed[sl];
+    hd = t.hd[sl];
+  }
+  constexpr int kVJunk = 0x100;  // votedFor outside [-1, P): as in k_election_rounds
+  const int pb = 1 << p;
+  int vb = voted == -1 ? 0 : ((unsigned)voted < (unsigned)P ? 1 << voted : kVJunk);
+  int upm = 0;  // bit c: candidate c's log is up to date for this voter (raft_log.go:99-104)
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    const int clt = __shfl(lterm, c, 8), clast = __shfl(last, c, 8);
+    upm |= (int)(clt > lterm || (clt == lterm && clast >= last)) << c;
+  }
+  __shared__ int lds_cx[256];
+  __shared__ __attribute__((aligned(8))) uint8_t lds_gm[256];
+  __shared__ int lds_rt[256];
+  __shared__ __attribute__((aligned(8))) uint8_t lds_rc[256];
+  const int seg = (int)(threadIdx.x & 63) & ~7;
+  int fl = 0, became = 0, pd = 0;
 
-// k_clock_round under a reachability mask (mraft_set_reachable): launched only
-// while a mask is set.
-template <int P>
-__global__ __launch_bounds__(256) void k_clock_round_reach(Dev s, TimerDev t, int now, unsigned flags,
-                                                           uint8_t *__restrict__ cand, int32_t *__restrict__ lpeer,
-                                                           int32_t *__restrict__ tg, int32_t *__restrict__ gflags,
-                                                           const uint8_t *__restrict__ reach) {
-  constexpr bool REACH = true;
-#include "mraft_clock_round_kernel.inc"
+  // A. ticker (raft.go:106-125). Every reset of this replica in this step
+  // happens at `now`, so they all set the same deadline.
+  const int ed_new = act ? election_deadline(t, sl, now) : 0;
+  const int hd_new = heartbeat_deadline(t, now);
+  const bool edue = act && ed <= now, hdue = act && hd <= now;
+  ed = edue ? ed_new : ed;                                             // :111
+  const bool fired = hdue && role == kLeader;                          // :119-121; its reset comes in C
+  hd = (hdue && role != kLeader) ? hd_new : hd;                        // :118
+  const int m = (int)((__ballot(edue) >> seg) & 0xffull);              // the round's timeouts (:112-114)
+
+  // B. one election round
+#include "mraft_elect_round.inc"
+  ed = (act && (gm & ~pb) != 0) ? ed_new : ed;                         // granted another replica, raft_election.go:72
+  hd = became ? hd_new : hd;                                           // :39
+
+  // C. the sender: highest currentTerm, lowest peer on a tie
+  const int elig = act && role == kLeader && (fired || became || (flags & MRAFT_CLOCK_SEND_ALL));
+  int bp = -1, bt = 0;
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    const int ce = __shfl(elig, c, 8), ct = __shfl(term, c, 8);
+    const bool take = ce && (bp < 0 || ct > bt);
+    bt = take ? ct : bt;
+    bp = take ? c : bp;
+  }
+  hd = (act && p == bp) ? hd_new : hd;
+
+  const unsigned long long el = __ballot(fl & MRAFT_G_ELECTED), sd = __ballot(fl & MRAFT_G_STEPPED_DOWN);
+  if (grp && p == 0) {
+    if (cand) cand[g] = (uint8_t)cm;
+    lpeer[g] = bp;
+    tg[g] = bt;
+    if (gflags)
+      gflags[g] = (((el >> seg) & 0xffull) ? MRAFT_G_ELECTED : 0) |
+                  (((sd >> seg) & 0xffull) ? MRAFT_G_STEPPED_DOWN : 0);
+  }
+  if (!act) return;
+  s.term[sl] = term;
+  s.voted[sl] = (vb & kVJunk) ? voted : (vb ? __builtin_ctz(vb) : -1);
+  s.role[sl] = role;
+  s.votes[sl] = votes;
+  t.ed[sl] = ed;
+  t.hd[sl] = hd;
+  if (pd) mark_persist(s, sl, MRAFT_PERSIST_STATE);
+  if (became) {
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      s.match[sl * P + j] = 0;
+      s.next[sl * P + j] = last + 1;
+    }
+  }
 }
 
 // E. the resets of the tick, from its group flags and the terms it left: a
 // follower whose term equals the sender's pre-tick term passed the term gate
 // of its handler (raft_append_entry.go:121, raft_snapshot.go:30); a sender
 // that stepped down reset its own timer (:71, raft_snapshot.go:63).
+// Under the reachability pack a non-sender heard the sender only when its bit
+// and the sender's are both set; without it the word is all-ones and `heard`
+// compiles to true. (A sender that is cut off folds no reply, so it never
+// carries STEPPED_DOWN.)
+template <class... M>
 __global__ __launch_bounds__(256) void k_clock_resets(Dev s, TimerDev t, int now,
                                                       const int32_t *__restrict__ gflags,
                                                       const int32_t *__restrict__ lpeer,
-                                                      const int32_t *__restrict__ tg) {
+                                                      const int32_t *__restrict__ tg,
+                                                      const M *__restrict__... reach) {
+  static_assert(sizeof...(M) <= 1, "the reachability pack holds no pointer or one");
   const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const int g = tid >> 3, p = tid & 7;
   if (g >= s.G || p >= s.P) return;
   const int gf = gflags[g];
   if (!(gf & MRAFT_G_ACTIVE) || (gf & MRAFT_G_ERROR)) return;
   const long long sl = (long long)g * s.P + p;
-  const bool hit = p != lpeer[g] ? s.term[sl] == tg[g] : (gf & MRAFT_G_STEPPED_DOWN) != 0;
-  if (hit) t.ed[sl] = election_deadline(t, sl, now);
-}
-
-// E under a reachability mask: a non-sender heard the sender only when its bit
-// and the sender's are both set; the rest of the rule is k_clock_resets'. (A
-// sender that is cut off folds no reply, so it never carries STEPPED_DOWN.)
-__global__ __launch_bounds__(256) void k_clock_resets_reach(Dev s, TimerDev t, int now,
-                                                            const int32_t *__restrict__ gflags,
-                                                            const int32_t *__restrict__ lpeer,
-                                                            const int32_t *__restrict__ tg,
-                                                            const uint8_t *__restrict__ reach) {
-  const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  const int g = tid >> 3, p = tid & 7;
-  if (g >= s.G || p >= s.P) return;
-  const int gf = gflags[g];
-  if (!(gf & MRAFT_G_ACTIVE) || (gf & MRAFT_G_ERROR)) return;
-  const long long sl = (long long)g * s.P + p;
-  const int lp = lpeer[g], rmask = (int)reach[g];
+  const int lp = lpeer[g], rmask = reach_byte(g, reach...);
   const bool heard = ((rmask >> p) & 1) && ((rmask >> (lp & 7)) & 1);
   const bool hit = p != lp ? heard && s.term[sl] == tg[g] : (gf & MRAFT_G_STEPPED_DOWN) != 0;
   if (hit) t.ed[sl] = election_deadline(t, sl, now);
@@ -241,27 +308,22 @@ void launch_timers_note(const TimerDev &t, int kind, const void *records, const 
 void launch_clock_round(const Dev &s, const TimerDev &t, int32_t now, uint32_t flags, uint8_t *cand,
                         int32_t *lpeer, int32_t *tg, int32_t *eflags, const uint8_t *reach, hipStream_t st) {
   const dim3 gr(blocks_for((int64_t)s.G * 8)), bl(256);
-  if (reach) {
-    with_peers<1>(s.P, [&](auto pc) {
-      hipLaunchKernelGGL(k_clock_round_reach<decltype(pc)::value>, gr, bl, 0, st, s, t, now, flags, cand, lpeer, tg,
-                         eflags, reach);
-    });
-    return;
-  }
   with_peers<1>(s.P, [&](auto pc) {
-    hipLaunchKernelGGL(k_clock_round<decltype(pc)::value>, gr, bl, 0, st, s, t, now, flags, cand, lpeer, tg, eflags);
+    constexpr int P = decltype(pc)::value;
+    if (reach)
+      hipLaunchKernelGGL((k_clock_round<P, uint8_t>), gr, bl, 0, st, s, t, now, flags, cand, lpeer, tg, eflags, reach);
+    else
+      hipLaunchKernelGGL(k_clock_round<P>, gr, bl, 0, st, s, t, now, flags, cand, lpeer, tg, eflags);
   });
 }
 
 void launch_clock_resets(const Dev &s, const TimerDev &t, int32_t now, const int32_t *gflags,
                          const int32_t *lpeer, const int32_t *tg, const uint8_t *reach, hipStream_t st) {
-  if (reach) {
-    hipLaunchKernelGGL(k_clock_resets_reach, dim3(blocks_for((int64_t)s.G * 8)), dim3(256), 0, st, s, t, now, gflags,
-                       lpeer, tg, reach);
-    return;
-  }
-  hipLaunchKernelGGL(k_clock_resets, dim3(blocks_for((int64_t)s.G * 8)), dim3(256), 0, st, s, t, now, gflags, lpeer,
-                     tg);
+  const dim3 gr(blocks_for((int64_t)s.G * 8)), bl(256);
+  if (reach)
+    hipLaunchKernelGGL(k_clock_resets<uint8_t>, gr, bl, 0, st, s, t, now, gflags, lpeer, tg, reach);
+  else
+    hipLaunchKernelGGL(k_clock_resets<>, gr, bl, 0, st, s, t, now, gflags, lpeer, tg);
 }
 
 }  // namespace mraft

@@ -13,6 +13,7 @@
 //  * wave_copy_from_ring — a ring row unrolled into a flat buffer
 //    (persistence read-out, staged entries);
 //  * wave_terms_sorted — whether a row's terms never decrease;
+// the optional reachability mask of a kernel (reach_given, reach_byte),
 // and for whole grids xcd_contiguous (each XCD a contiguous range of the
 // workgroups) and compact_count / compact_offsets, the in-block part of an
 // ordered compaction of K lists (the compacted applier, the ticker). The
@@ -203,6 +204,22 @@ __device__ __forceinline__ T xcd_contiguous(T b, T nb) {
   const T x = b & 7, per = nb >> 3, rem = nb & 7;
   return x * per + min(x, rem) + (b >> 3);
 }
+
+// ---------------------------------------------------------------- reachability mask
+// Convention: a kernel that can run under a reachability mask
+// (mraft_set_reachable) takes as its last parameter a pack of no pointer or
+// one, `const M *__restrict__... reach`: empty, the kernel is the unmasked one;
+// M = uint8_t, it reads the groups' reachability bytes.
+template <class... M>
+constexpr bool reach_given() {
+  static_assert(sizeof...(M) <= 1, "the reachability pack holds no pointer or one");
+  return sizeof...(M) == 1;
+}
+
+// Group g's reachability word (bit p: replica p is connected): the constant
+// all-ones without a mask, so every test of it compiles away.
+__device__ __forceinline__ int reach_byte(int) { return -1; }
+__device__ __forceinline__ int reach_byte(int g, const uint8_t *m) { return (int)m[g]; }
 
 // ---------------------------------------------------------------- ordered compaction
 // K lists of the items that satisfy K predicates, each in ascending item

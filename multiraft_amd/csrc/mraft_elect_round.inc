@@ -9,9 +9,9 @@
 //   the accumulators fl, became, pd, and the __shared__ arrays lds_cx, lds_gm,
 //   lds_rt, lds_rc (256 entries each);
 //   REACH (constexpr bool) and rmask, the group's reachability word
-//   (mraft_set_reachable, bit q: replica q is connected). The unmasked kernels
-//   say REACH = false with rmask the constant all-ones, and every test of it
-//   compiles away. Under a mask candidate c's RequestVote reaches voter v, and
+//   (mraft_set_reachable, bit q: replica q is connected). A kernel without the
+//   reachability pack (mraft_device.h) has REACH = false with rmask the
+//   constant all-ones, and every test of it compiles away. Under a mask candidate c's RequestVote reaches voter v, and
 //   v's reply reaches c, iff both their bits are set; timeouts and
 //   StartElection are local and happen either way.
 // It leaves in scope: isc (this lane ran StartElection), gm (bit c: this voter

@@ -138,7 +138,7 @@ struct mraft_engine {
   mraft_timer_config tcfg{};
   // Reachability (mraft_set_reachable): the engine's copy of the mask, one
   // byte per group, or null when none is set (everyone connected). While it is
-  // set the co-resident calls launch their *_reach kernels with it.
+  // set the co-resident calls launch their kernels' masked instances with it.
   uint8_t *reach = nullptr;
   void *scratch_ptr[kScrSlots] = {};
   size_t scratch_cap[kScrSlots] = {};

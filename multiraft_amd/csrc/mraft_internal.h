@@ -198,8 +198,9 @@ size_t fold_scan_bytes(int64_t n, int64_t n_seg);  // scratch launch_fold needs 
 // ---------------------------------------------------------------- mraft_tick.hip
 // `reach` (here and in every launcher below that takes it): the groups'
 // reachability bytes (mraft_set_reachable), or null when no mask is set. Null
-// launches the kernels as they are without the feature; a mask launches their
-// *_reach counterparts, which compile the same bodies with the mask's tests.
+// launches the kernels as they are without the feature; a mask launches the
+// same templates with the reachability pack (mraft_device.h), which compiles
+// the mask's tests into their bodies.
 void launch_replicate_tick(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
                            int32_t *exp_term_leader, const uint8_t *reach, hipStream_t st);
 // The light tick (MRAFT_TICK_LIGHT): k_tick_lite (mraft_tick_lite.hip)
@@ -255,11 +256,6 @@ void launch_replicate_tick_light(const Dev &s, const int32_t *lpeer, int32_t *gf
 // ---------------------------------------------------------------- mraft_elect.hip
 void launch_election_rounds(const Dev &s, const uint8_t *cand, int R, int32_t *gflags, const uint8_t *reach,
                             hipStream_t st);
-
-// ---------------------------------------------------------------- mraft_elect_reach.hip
-// The storm under a mask (reach non-null); launch_election_rounds calls it.
-void launch_election_rounds_reach(const Dev &s, const uint8_t *cand, int R, int32_t *gflags, const uint8_t *reach,
-                                  hipStream_t st);
 
 // ---------------------------------------------------------------- mraft_clock.hip
 // Timers (include/mraft.h "timers"): the two deadline arrays of a handle with

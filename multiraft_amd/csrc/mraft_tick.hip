@@ -186,15 +186,18 @@ __device__ __forceinline__ unsigned long long tick_xcc() {
 // the compare chunks without software pipelining, two dwordx4 per lane per
 // chunk and the state pointers held across the pass all measured slower; git
 // history keeps them).
-
-template <int P, bool COUNT>
+//
+// With the reachability pack (mraft_device.h; mraft_set_reachable) the body
+// runs with REACH, reach[g] one more wave-uniform byte of its header. Launched
+// so only while a mask is set, and never with COUNT
+// (mraft_replicate_tick_count is defined for the full network only).
+template <int P, bool COUNT, class... M>
 __global__ __launch_bounds__(64, MRAFT_TICK_MINW) void k_tick_group(Dev s, const int32_t *__restrict__ leader_peer,
                                                     int32_t *__restrict__ gflags,
-                                                    unsigned long long *__restrict__ counts,
-                                                    Export ex) {
+                                                    unsigned long long *__restrict__ counts, Export ex,
+                                                    const M *__restrict__... reach) {
   constexpr int NI = P - 1;
-  constexpr bool REACH = false;  // no reachability mask: the body's word is the constant all-ones
-  constexpr const uint8_t *reach = nullptr;
+  constexpr bool REACH = reach_given<M...>();
   const int lane = lane_id();
   // Each XCD a contiguous range of groups, so the scalar SoA lines
   // neighbouring groups share stay in one XCD's L2. Speed only; any placement
@@ -203,26 +206,6 @@ __global__ __launch_bounds__(64, MRAFT_TICK_MINW) void k_tick_group(Dev s, const
   // (threadIdx.x >> 6 is 0 in a one-wave workgroup; without the term the
   // compiler assigns this kernel's registers differently, so the measured
   // code is kept instruction-for-instruction)
-  const int g = uni(gb + (int)(threadIdx.x >> 6));
-  if (g >= s.G) return;
-#define TICK_EXIT return
-#include "mraft_tick_body.inc"
-#undef TICK_EXIT
-}
-
-// k_tick_group under a reachability mask (mraft_set_reachable): the same body
-// with REACH, reach[g] one more wave-uniform byte of the header. Launched only
-// while a mask is set; never counts (mraft_replicate_tick_count is defined for
-// the full network only).
-template <int P>
-__global__ __launch_bounds__(64, MRAFT_TICK_MINW) void k_tick_group_reach(Dev s, const int32_t *__restrict__ leader_peer,
-                                                          int32_t *__restrict__ gflags,
-                                                          unsigned long long *__restrict__ counts, Export ex,
-                                                          const uint8_t *__restrict__ reach) {
-  constexpr bool COUNT = false, REACH = true;
-  constexpr int NI = P - 1;
-  const int lane = lane_id();
-  const int gb = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
   const int g = uni(gb + (int)(threadIdx.x >> 6));
   if (g >= s.G) return;
 #define TICK_EXIT return
@@ -265,52 +248,18 @@ __global__ void k_tick_p1(Dev s, const int32_t *__restrict__ leader_peer,
 // exact; the host sizes it from the previous tick's count). The first
 // workgroup zeroes the counters the next light tick uses and publishes this
 // tick's count to the host's pinned word.
-template <int P>
+// Under a reachability pack the walk is the same and the body runs with
+// REACH: the masked light launch (mraft_tick_lite.hip) lists every group whose
+// mask is incomplete, so this is where a partitioned group's tick runs in
+// light mode.
+template <int P, class... M>
 __global__ __launch_bounds__(64, MRAFT_TICK_MINW) void k_tick_list(Dev s, const int32_t *__restrict__ leader_peer,
                                                    int32_t *__restrict__ gflags,
                                                    unsigned long long *__restrict__ counts, Export ex,
                                                    const int32_t *__restrict__ list, const unsigned *__restrict__ cnt,
                                                    unsigned *__restrict__ cnt_next, long long *__restrict__ hint,
-                                                   int cap) {
-  constexpr bool COUNT = false, REACH = false;
-  constexpr const uint8_t *reach = nullptr;
-  constexpr int NI = P - 1;
-  const int lane = lane_id();
-  unsigned c8[8], nl = 0;
-#pragma unroll
-  for (int x = 0; x < 8; ++x) {
-    c8[x] = (unsigned)uni((int)cnt[x * kLiteCntStride]);
-    nl += c8[x];
-  }
-  if (blockIdx.x == 0) {
-    if (lane < 8) cnt_next[lane * kLiteCntStride] = 0;
-    if (lane == 0 && hint) __hip_atomic_store(hint, (long long)nl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  for (unsigned k = blockIdx.x; k < nl; k += gridDim.x) {
-    unsigned base = 0;
-    int x = 0;
-#pragma unroll
-    for (int y = 0; y < 7; ++y)
-      if (x == y && k >= base + c8[y]) { base += c8[y]; x = y + 1; }
-    const int g = uni(list[(long long)x * cap + (k - base)]);
-#define TICK_EXIT continue
-#include "mraft_tick_body.inc"
-#undef TICK_EXIT
-  }
-}
-
-// k_tick_list under a reachability mask: the walk over the lists is
-// k_tick_list's, the body runs with REACH. The masked light launch
-// (mraft_tick_lite.hip) lists every group whose mask is incomplete, so this is
-// where a partitioned group's tick runs in light mode.
-template <int P>
-__global__ __launch_bounds__(64, MRAFT_TICK_MINW) void k_tick_list_reach(Dev s, const int32_t *__restrict__ leader_peer,
-                                                         int32_t *__restrict__ gflags,
-                                                         unsigned long long *__restrict__ counts, Export ex,
-                                                         const int32_t *__restrict__ list, const unsigned *__restrict__ cnt,
-                                                         unsigned *__restrict__ cnt_next, long long *__restrict__ hint,
-                                                         int cap, const uint8_t *__restrict__ reach) {
-  constexpr bool COUNT = false, REACH = true;
+                                                   int cap, const M *__restrict__... reach) {
+  constexpr bool COUNT = false, REACH = reach_given<M...>();
   constexpr int NI = P - 1;
   const int lane = lane_id();
   unsigned c8[8], nl = 0;
@@ -367,26 +316,24 @@ void launch_replicate_tick(const Dev &s, const int32_t *lpeer, int32_t *gflags, 
   const Export ex{exp_commit, exp_term_leader};
   // P == 1 sends nothing: its kernel is the same with and without a mask
   if (!reach || !with_peers<2>(s.P, [&](auto pc) {
-        hipLaunchKernelGGL(k_tick_group_reach<decltype(pc)::value>, dim3(s.G), dim3(64), 0, st, s, lpeer, gflags,
-                           (unsigned long long *)nullptr, ex, reach);
+        hipLaunchKernelGGL((k_tick_group<decltype(pc)::value, false, uint8_t>), dim3(s.G), dim3(64), 0, st, s, lpeer,
+                           gflags, (unsigned long long *)nullptr, ex, reach);
       }))
     launch_tick_c<false>(s, lpeer, gflags, nullptr, ex, st);
 }
 
 void launch_tick_list(const Dev &s, const int32_t *lpeer, int32_t *gflags, int32_t *exp_commit,
                       int32_t *exp_term_leader, const LiteBufs &lb, const uint8_t *reach, hipStream_t st) {
-  if (reach) {
-    with_peers<2>(s.P, [&](auto pc) {
-      hipLaunchKernelGGL(k_tick_list_reach<decltype(pc)::value>, dim3((unsigned)lb.grid), dim3(64), 0, st, s, lpeer,
-                         gflags, (unsigned long long *)nullptr, Export{exp_commit, exp_term_leader},
-                         (const int32_t *)lb.list, (const unsigned *)lb.cnt, lb.cnt_next, lb.hint, lite_cap(s.G), reach);
-    });
-    return;
-  }
   with_peers<2>(s.P, [&](auto pc) {
-    hipLaunchKernelGGL(k_tick_list<decltype(pc)::value>, dim3((unsigned)lb.grid), dim3(64), 0, st, s, lpeer, gflags,
-                       (unsigned long long *)nullptr, Export{exp_commit, exp_term_leader}, (const int32_t *)lb.list,
-                       (const unsigned *)lb.cnt, lb.cnt_next, lb.hint, lite_cap(s.G));
+    constexpr int P = decltype(pc)::value;
+    const dim3 gr((unsigned)lb.grid), bl(64);
+    const Export ex{exp_commit, exp_term_leader};
+    if (reach)
+      hipLaunchKernelGGL((k_tick_list<P, uint8_t>), gr, bl, 0, st, s, lpeer, gflags, nullptr, ex, lb.list, lb.cnt,
+                         lb.cnt_next, lb.hint, lite_cap(s.G), reach);
+    else
+      hipLaunchKernelGGL((k_tick_list<P>), gr, bl, 0, st, s, lpeer, gflags, nullptr, ex, lb.list, lb.cnt,
+                         lb.cnt_next, lb.hint, lite_cap(s.G));
   });
 }
 

@@ -6,16 +6,15 @@
 // tick's fallback: the groups of a device list, grid-stride). Expects P, COUNT,
 // NI, lane, g, s (Dev, the kernel's first argument: reload_dev), leader_peer,
 // gflags, counts, ex in scope and TICK_EXIT defined (return / continue); and
-// REACH (constexpr bool) with reach, the groups' reachability bytes
-// (mraft_set_reachable): the unmasked kernels say REACH = false, which makes
-// the group's reachability word the constant all-ones and every test of it
-// compile away.
+// REACH (constexpr bool) with reach, the kernel's reachability pack
+// (mraft_device.h): empty, REACH is false, the group's reachability word is
+// the constant all-ones and every test of it compiles away.
   const int L = s.L;
   TICK_STAMP(0);
 
   // ------------------------------------------------------------ header
   const int lp = uni(leader_peer[g]);
-  const int rmask = REACH ? uni((int)reach[g]) : -1;  // bit p: replica p is connected
+  const int rmask = uni(reach_byte(g, reach...));  // bit p: replica p is connected
   if (lp < 0 || lp >= P) {
     if (!COUNT && lane == 0) {
       if (gflags) gflags[g] = lp >= P ? MRAFT_G_ERROR : 0;

@@ -54,7 +54,8 @@ def test_unit_identical_to_itself(tmp_path):
     old = isa_diff.tree_kernels(ROOT, str(tmp_path), "old", ["mraft_elect.hip"])
     new = isa_diff.tree_kernels(ROOT, str(tmp_path), "new", ["mraft_elect.hip"])
     rows = isa_diff.compare(old, new)
-    assert len(rows) == 8 and all(v == "IDENTICAL" for v, _ in rows), rows  # k_election_rounds<1..8>
+    # k_election_rounds<1..8>, without and with the reachability pack
+    assert len(rows) == 16 and all(v == "IDENTICAL" for v, _ in rows), rows
     # and a kernel whose code changed is told apart
     name = next(iter(new))
     new[name] = (new[name][0], new[name][1][:-1])

@@ -1,7 +1,7 @@
 """Whether two source trees compile to the same gfx950 device code, kernel by
 kernel: the check a refactor of the kernel units has to pass. CPU only.
 
-  python3 tools/isa_diff.py OLD_TREE NEW_TREE [--only UNIT.hip ...]
+  python3 tools/isa_diff.py OLD_TREE NEW_TREE [--only UNIT.hip ...] [--rename REGEX=REPLACEMENT ...]
 
 Every .hip unit under each tree's multiraft_amd/csrc is compiled to device
 assembly (the Makefile's HIPFLAGS of that tree plus --offload-device-only -S,
@@ -14,6 +14,8 @@ normalised. A kernel is named by its demangled name without the parameter
 list, so a kernel may move to another unit, or a parameter type to another
 namespace, and still be matched. Prints IDENTICAL / DIFFERS / ONLY-IN-ONE per
 kernel; exits 0 only when both trees hold the same kernels, all identical.
+--rename REGEX=REPLACEMENT (repeatable, re.sub on the old tree's kernel names
+before matching) pairs a kernel the new tree renamed with its old self.
 
 The old tree is usually the parent commit:
   git archive HEAD | tar -x -C /tmp/parent
@@ -143,10 +145,17 @@ def main() -> int:
     ap.add_argument("old_tree")
     ap.add_argument("new_tree")
     ap.add_argument("--only", nargs="*", default=[], help="unit file names to compare (default: every .hip unit)")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPLACEMENT",
+                    help="applied to the old tree's kernel names before matching (repeatable)")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         old = tree_kernels(a.old_tree, tmp, "old", a.only)
         new = tree_kernels(a.new_tree, tmp, "new", a.only)
+    for pattern, replacement in (r.split("=", 1) for r in a.rename):
+        renamed = {re.sub(pattern, replacement, name): kernel for name, kernel in old.items()}
+        if len(renamed) != len(old):
+            raise RuntimeError(f"--rename {pattern}={replacement} maps two kernels of the old tree to one name")
+        old = renamed
     rows = compare(old, new)
     for verdict, what in rows:
         print(f"{verdict:12s}{what}")
