@@ -3,11 +3,11 @@
 // The replica state every kernel takes (Dev), the log ring (ring, term_at),
 // mark_persist, and the 64-lane wave's helpers (lane_id, first_lane, uni,
 // wave_sum), then its wave-cooperative primitives over a ring row:
-//  * wave_scan_down_ne / wave_scan_down_eq — the highest Index of a range
-//    whose term differs from / equals a value, 256 terms per iteration (4
-//    coalesced dword loads per lane in flight), found by ballot + find-first-set
-//    (the ConflictIndex scan; the term gate of advanceCommitIndexForLeader,
-//    raft_append_entry.go:89-105);
+//  * wave_scan_down (wave_scan_down_ne / wave_scan_down_eq) — the highest
+//    Index of a range whose term differs from / equals a value, 64·U terms
+//    per iteration (U coalesced dword loads per lane in flight), found by
+//    ballot + find-first-set (the ConflictIndex scan; the term gate of
+//    advanceCommitIndexForLeader, raft_append_entry.go:89-105);
 //  * wave_conflict_scan — the ConflictIndex backward scan of :136-142;
 //  * wave_copy — a streaming copy into a replica's log (restore);
 //  * wave_copy_from_ring — a ring row unrolled into a flat buffer
@@ -66,28 +66,30 @@ __device__ __forceinline__ int first_lane(unsigned long long m) { return __ffsll
 // A value every lane of the wave holds alike, in an SGPR.
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// Largest idx in [lo, hi] with term(idx) != a, scanning downward, in a ring
-// row whose Index `base` (the dummy) sits at `head` (row length L); returns
-// lo - 1 when every term in the range equals a. Wave-uniform arguments; the
-// term of lo must be readable when lo <= hi (lanes past lo re-read it).
-template <int U = kUnroll>
-__device__ __forceinline__ int wave_scan_down_ne(const int32_t *__restrict__ row, int base, int head,
-                                                 int L, int lo, int hi, int a) {
+// The downward term scan: the largest idx in [lo, hi] whose term equals a
+// (EQ) or differs from it (!EQ), in a ring row whose Index `base` (the dummy)
+// sits at `head` (row length L); lo - 1 when no term of the range does.
+// 64·U terms per iteration (U coalesced dword loads per lane in flight),
+// found by ballot + find-first-set. Wave-uniform arguments; the term of lo
+// must be readable when lo <= hi (lanes past lo re-read it).
+template <bool EQ, int U>
+__device__ __forceinline__ int wave_scan_down(const int32_t *__restrict__ row, int base, int head, int L,
+                                              int lo, int hi, int a) {
   const int lane = lane_id();
   for (int top = hi; top >= lo; top -= kWave * U) {
     int v[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int idx = top - lane - kWave * u;
-      const int w = row[ring(max(idx, lo) - base + head, L)];  // unconditional: the loads issue back to back
-      v[u] = idx >= lo ? w : a;
+      const int w = row[ring(max(idx, lo) - base + head, L)];  // unconditional: the U loads issue back to back
+      v[u] = idx >= lo ? w : EQ ? a + 1 : a;                   // past lo: a term that does not count
     }
     // Every ballot, no exit per vector (which lets the compiler sink each load
     // behind the previous compare: one round trip per 64 terms).
     int r = lo - 1;
 #pragma unroll
     for (int u = U - 1; u >= 0; --u) {
-      const unsigned long long m = __ballot(v[u] != a);
+      const unsigned long long m = __ballot(EQ ? v[u] == a : v[u] != a);
       r = m ? top - kWave * u - first_lane(m) : r;
     }
     if (r >= lo) return r;
@@ -95,27 +97,17 @@ __device__ __forceinline__ int wave_scan_down_ne(const int32_t *__restrict__ row
   return lo - 1;
 }
 
-// Largest idx in [lo, hi] with term(idx) == a (ring row as above); lo - 1 if none.
+// Its two uses by name: the ConflictIndex scan (term differs), and the term
+// gate of advanceCommitIndexForLeader (term equals; a1 of the reply fold).
+template <int U = kUnroll>
+__device__ __forceinline__ int wave_scan_down_ne(const int32_t *__restrict__ row, int base, int head,
+                                                 int L, int lo, int hi, int a) {
+  return wave_scan_down<false, U>(row, base, head, L, lo, hi, a);
+}
+template <int U = kUnroll>
 __device__ __forceinline__ int wave_scan_down_eq(const int32_t *__restrict__ row, int base, int head,
                                                  int L, int lo, int hi, int a) {
-  const int lane = lane_id();
-  for (int top = hi; top >= lo; top -= kChunk) {
-    int v[kUnroll];
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      const int idx = top - lane - kWave * u;
-      const int w = row[ring(max(idx, lo) - base + head, L)];
-      v[u] = idx >= lo ? w : a + 1;
-    }
-    int r = lo - 1;
-#pragma unroll
-    for (int u = kUnroll - 1; u >= 0; --u) {
-      const unsigned long long m = __ballot(v[u] == a);
-      r = m ? top - kWave * u - first_lane(m) : r;
-    }
-    if (r >= lo) return r;
-  }
-  return lo - 1;
+  return wave_scan_down<true, U>(row, base, head, L, lo, hi, a);
 }
 
 // ConflictIndex of raft_append_entry.go:136-142 for prev > dummy + 1, where

@@ -41,14 +41,6 @@ __global__ void k_claim_zero(const char *__restrict__ items, int64_t n, int stri
 }
 
 // ---------------------------------------------------------------- a2 + a1
-// A reply record inside the Index domain (include/mraft.h): the acknowledged
-// entries end at prevLogIndex + n <= 2^31 - 2 with n >= 0 (matchIndex and
-// nextIndex stay int32); else the segment is malformed, as in the oracle
-// (reply_index_ok).
-__device__ __forceinline__ bool reply_index_ok(int prev, int n) {
-  return n >= 0 && index_in_domain((int64_t)prev + n);
-}
-
 #ifndef MRAFT_FOLD_GRID
 #define MRAFT_FOLD_GRID (1 << 30)  // workgroups of the reply fold (segments beyond: grid-stride)
 #endif
@@ -78,42 +70,6 @@ constexpr int kFoldScanU = 4;               // long-segment a1 scan: dword loads
 constexpr int kFscanU = 8;                  // k_fold_tail scans: dword loads per lane in flight (4: +7 %)
 constexpr int kFscanW = 4;                  // pending a1 ranges per k_fold_tail scan wave
 
-// One iteration of the a1 scan: the highest idx in [max(lo, top - 64·U + 1),
-// top] with row[idx] == a, or lo - 1 (wave-uniform arguments).
-template <int U>
-__device__ __forceinline__ int fold_scan_iter(const int32_t *__restrict__ row, int base, int head, int L,
-                                              int lo, int top, int a) {
-  const int lane = lane_id();
-  int v[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int idx = top - lane - kWave * u;
-    const int w = row[ring(max(idx, lo) - base + head, L)];  // unconditional: the U loads issue back to back
-    v[u] = idx >= lo ? w : a + 1;
-  }
-  // Every ballot of the iteration (no early exit: an exit per vector lets
-  // the compiler sink each load behind the previous compare).
-  int r = lo - 1;
-#pragma unroll
-  for (int u = U - 1; u >= 0; --u) {
-    const unsigned long long m = __ballot(v[u] == a);
-    r = m ? top - kWave * u - first_lane(m) : r;
-  }
-  return r;
-}
-
-// Highest idx in [lo, hi] with row[idx - base] == a, or lo - 1: the a1 scan
-// of the reply fold, 64·U terms per round trip.
-template <int U>
-__device__ __forceinline__ int fold_scan_down_eq(const int32_t *__restrict__ row, int base, int head, int L,
-                                                 int lo, int hi, int a) {
-  if (hi < lo) return lo - 1;
-  int r = fold_scan_iter<U>(row, base, head, L, lo, hi, a);
-  for (int top = hi - kWave * U; r < lo && top >= lo; top -= kWave * U)
-    r = fold_scan_iter<U>(row, base, head, L, lo, top, a);
-  return r;
-}
-
 // Appends the lanes' pending a1 ranges (pred) to k_fold_tail's compact list:
 // one atomic per wave on the list's counter. Record: {lo, hi, slot,
 // currentTerm}, {dummy, ring head, reply index, 0}. Wave-uniform call.
@@ -132,162 +88,172 @@ __device__ __forceinline__ void push_pending(int4 *__restrict__ pend, unsigned *
   }
 }
 
-// A long segment (more replies than a lane group: k_fold_tail), one wave.
-// Lane k loads reply k of a 64-reply batch, so a segment's replies arrive in
-// one round trip; the fold
-// (a2, :66-88) then runs over them in array order on wave-uniform values.
-// a1 (:89-105) is evaluated after each successful reply exactly as :78 calls
-// it, but its log reads are deferred to the end of the batch: the fold never
-// reads commitIndex, and while the replica stays leader its term is the
-// segment's initial term, so every evaluation is "the highest index in
-// (H, top] whose term is currentTerm", with H the largest top evaluated so
-// far (an evaluation that scanned (commit, top] leaves no entry of that term
-// above the new commit up to top). The ranges of one batch are disjoint and
-// ascending: their top words are probed in parallel (one round trip; on a
-// log whose last entries carry the current term, every range ends there) and
-// only ranges whose top word differs are scanned, wave-cooperatively.
+// Lane groups of GW lanes (the wave as 64 / GW groups; GW = 64: the wave).
+template <int GW>
+__device__ __forceinline__ int gw_base() { return (int)(lane_id() & ~(unsigned)(GW - 1)); }
+template <int GW>
+__device__ __forceinline__ auto gw_mask(bool pred) {  // this lane's group's ballot, bit k = its lane k
+  if constexpr (GW == 64) return __ballot(pred);
+  else return (unsigned)((__ballot(pred) >> gw_base<GW>()) & ((1ull << GW) - 1));
+}
+template <int GW>
+__device__ __forceinline__ int gw_bcast(int v, int k) { return __shfl(v, gw_base<GW>() + k, 64); }
+__device__ __forceinline__ int last_lane(unsigned m) { return 31 - __clz((int)m); }
+__device__ __forceinline__ int last_lane(unsigned long long m) { return 63 - __builtin_clzll(m); }
+
+// ---------------------------------------------------------------- the fold's rules
+// processAppendEntriesReply + advanceCommitIndexForLeader
+// (raft_append_entry.go:66-105) on one reply segment, each rule stated once
+// for the fold's two paths (fold_segment, one segment per wave; fold_groupw,
+// one per lane group). The lanes that share a segment hold its running values
+// alike; "this lane's" values belong to the reply the lane owns.
+
+// The item segment sg begins at (segment sg - 1 ends before it); without
+// seg_begin every item is a segment of its own. segment_bounds (mraft_rules.h)
+// by value, for the group path.
+__device__ __forceinline__ int64_t segment_edge(const int64_t *__restrict__ seg_begin, int64_t sg) {
+  return seg_begin ? seg_begin[sg] : sg;
+}
+
+// Whether segment sg owns the slot whose claim word is (cw_hi, cw_lo): items
+// addressed to one replica slot in several segments, the lowest segment wins
+// (k_claim_zero's atomicMax on the inverted index), the others are rejected
+// before any state change. The same truth as claim_won(word, epoch, sg); on
+// the halves, because the long path holds the low half wave-uniform and the
+// high half is the epoch itself: two 32-bit compares, no 64-bit tag formed.
+__device__ __forceinline__ bool claim_owned(uint32_t cw_lo, uint32_t cw_hi, uint32_t epoch, int64_t sg) {
+  return cw_lo == (uint32_t)claim_tag(epoch, sg) && cw_hi == epoch;
+}
+
+// A reply that makes its segment malformed: another slot than the segment's,
+// a peer outside the group or the replica itself, or a record outside the
+// Index domain (include/mraft.h; the oracle's reply_index_ok): the
+// acknowledged entries end at prevLogIndex + n <= 2^31 - 2 with n >= 0, so
+// matchIndex and nextIndex stay int32.
 template <int P>
-__device__ __forceinline__ void fold_segment(const Dev &s, const mraft_ae_result *__restrict__ items,
-                                             const int64_t *__restrict__ seg_begin, int64_t sg,
-                                             const int32_t *__restrict__ seg_err,
-                                             const unsigned long long *__restrict__ claim, uint32_t epoch,
-                                             int32_t *__restrict__ flags, int32_t *__restrict__ item_err) {
-  const int lane = lane_id();
-  const int64_t b = seg_begin ? seg_begin[sg] : sg, e = seg_begin ? seg_begin[sg + 1] : sg + 1;
-  int bad = uni(seg_err[sg]);  // the claim verdict: a bad segment's slot may be out of range
-  if (b >= e) return;
-  const int64_t cnt = e - b;
-  mraft_ae_result it{};
-  if (lane < cnt) it = items[b + lane];
-  const int slot = __builtin_amdgcn_readfirstlane(it.slot);
-  const int me = slot % P;
-  const int64_t mrow = (int64_t)slot * P;
-  // The replica's state in one round trip: one load per lane, lanes 0..P-1
-  // matchIndex, 8..8+P-1 nextIndex, 16..20 the scalars.
-  const int32_t *src = nullptr;
-  int64_t si = slot;
-  if (lane < P) { src = s.match; si = mrow + lane; }
-  else if (lane >= 8 && lane < 8 + P) { src = s.next; si = mrow + lane - 8; }
-  else if (lane == 16) src = s.term;
-  else if (lane == 17) src = s.role;
-  else if (lane == 18) src = s.commit;
-  else if (lane == 19) src = s.last;
-  else if (lane == 20) src = s.dummy;
-  else if (lane == 21) src = s.head;
-  else if (lane == 22) src = s.srt;
-  const int vs = (src && !bad) ? src[si] : 0;
-  // items addressed to one replica slot in several segments: the lowest
-  // segment wins (k_claim_zero's atomicMax on the inverted index), the others
-  // are rejected before any state change — loaded beside the state
-  const unsigned long long cw = !bad ? claim[slot] : 0ull;
-  // (claim_won(cw, epoch, sg), the halves of claim_tag compared apart)
-  if (!bad && __builtin_amdgcn_readfirstlane((int)(uint32_t)cw) != (int)(uint32_t)claim_tag(epoch, sg)) bad = MRAFT_ITEM_DUP_SLOT;
-  if (!bad && (uint32_t)(cw >> 32) != epoch) bad = MRAFT_ITEM_DUP_SLOT;
-  int term = __builtin_amdgcn_readlane(vs, 16), role = __builtin_amdgcn_readlane(vs, 17),
-      commit = __builtin_amdgcn_readlane(vs, 18);
-  const int last = __builtin_amdgcn_readlane(vs, 19), dummy = __builtin_amdgcn_readlane(vs, 20),
-            head = __builtin_amdgcn_readlane(vs, 21), srt = __builtin_amdgcn_readlane(vs, 22);
-  for (int64_t base = 0; base < cnt; base += 64) {
-    const int64_t i = base + lane;
-    int sl = it.slot, pr = it.peer;
-    if (base > 0 && i < cnt) { sl = items[b + i].slot; pr = items[b + i].peer; }
-    // (a segment that does not own its slot stays MRAFT_ITEM_DUP_SLOT: the
-    // claim decides first, include/mraft.h)
-    bool dok = true;  // the record inside the Index domain (reply_index_ok)
-    if (i < cnt) {
-      const mraft_ae_result &r = base > 0 ? items[b + i] : it;
-      dok = reply_index_ok(r.args_prev_log_index, r.args_n_entries);
-    }
-    if (__ballot(i < cnt && (sl != slot || pr < 0 || pr >= P || pr == me || !dok)) && !bad) bad = MRAFT_ITEM_BAD_SLOT;
-  }
-  if (!bad && commit < dummy) bad = MRAFT_ITEM_BAD_STATE;
-  if (bad) {
-    for (int64_t i = lane; i < cnt; i += 64) { item_err[b + i] = bad; flags[b + i] = 0; }
-    return;
-  }
-  int m[8], nx[8];
+__device__ __forceinline__ bool reply_malformed(const mraft_ae_result &r, int slot, int me) {
+  return r.slot != slot || r.peer < 0 || r.peer >= P || r.peer == me || r.args_n_entries < 0 ||
+         !index_in_domain((int64_t)r.args_prev_log_index + r.args_n_entries);
+}
+
+// The verdict on a segment before any state changes, in the order of
+// include/mraft.h: the claim's error or a slot another segment owns (bad, on
+// entry: the claim decides first), then a malformed reply, then a replica
+// whose commitIndex lies below its dummy.
+__device__ __forceinline__ int fold_verdict(int bad, bool malformed, int commit, int dummy) {
+  if (bad) return bad;
+  if (malformed) return MRAFT_ITEM_BAD_SLOT;
+  return commit < dummy ? MRAFT_ITEM_BAD_STATE : 0;
+}
+
+// A reply's fields as the reply step reads them, r(&mraft_ae_result::field),
+// each path in its own fetch order. LaneReply: reply k of the long path's
+// batch sits in lane k, and a field is read there when the step needs it
+// (success, the entry count and the conflict index only inside their branch).
+// HeldReply: the group path has broadcast the whole record up front.
+using ReplyField = int32_t mraft_ae_result::*;
+struct LaneReply {
+  const mraft_ae_result &it;
+  int k;
+  __device__ __forceinline__ int operator()(ReplyField f) const { return __builtin_amdgcn_readlane(it.*f, k); }
+};
+struct HeldReply {
+  mraft_ae_result v;
+  __device__ __forceinline__ int operator()(ReplyField f) const { return v.*f; }
+};
+
+// The reply step (:67-88) on the segment's running values; returns the
+// reply's flags. a1 (:89-105) is evaluated after each successful reply exactly
+// as :78 calls it, but its log reads are deferred: the fold never reads
+// commitIndex, and while the replica stays leader its term is the segment's
+// initial term, so every evaluation is "the highest index in (H, top] whose
+// term is currentTerm", with H the largest top evaluated so far (an
+// evaluation that scanned (commit, top] leaves no entry of that term above
+// the new commit up to top). The lane that owns reply k (ln == k, ln the
+// lane's position in its segment) keeps the range as (plo, phi); a segment's
+// ranges are disjoint and ascending. (ln and k apart, not the bool ln == k:
+// as a lane mask held across the step it costs both kernels scalar registers.)
+template <int P, class Reply>
+__device__ __forceinline__ int reply_step(const Reply &r, int ln, int k, int &term, int &role, int (&m)[8],
+                                          int (&nx)[8], int &H, int last, int me, bool &touched_mn, int &plo,
+                                          int &phi) {
+  using R = mraft_ae_result;
+  const int pr = r(&R::peer), rt = r(&R::reply_term), at = r(&R::args_term), ap = r(&R::args_prev_log_index);
+  int fl = 0, nxp = 0;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    m[j] = j < P ? __builtin_amdgcn_readlane(vs, j) : 0;
-    nx[j] = j < P ? __builtin_amdgcn_readlane(vs, 8 + j) : 0;
-  }
-  const int c0 = commit, t0 = term, r0 = role;
-  const int32_t *lrow = s.log + (int64_t)slot * s.L;
-  bool touched_mn = false;
-  int H = commit;
-  for (int64_t base = 0; base < cnt; base += 64) {
-    if (base > 0 && base + lane < cnt) it = items[b + base + lane];
-    const int nb = (int)min((int64_t)64, cnt - base);
-    int myfl = 0, plo = 1, phi = 0;  // this lane's reply: flags and a1 range
-    for (int k = 0; k < nb; ++k) {
-      const int pr = __builtin_amdgcn_readlane(it.peer, k);
-      const int rt = __builtin_amdgcn_readlane(it.reply_term, k);
-      const int at = __builtin_amdgcn_readlane(it.args_term, k);
-      const int ap = __builtin_amdgcn_readlane(it.args_prev_log_index, k);
-      int fl = 0, nxp = 0;
+  for (int j = 0; j < P; ++j) if (j == pr) nxp = nx[j];
+  if (rt > term) {                                                       // :67-72
+    term = rt; role = kFollower;
+    fl |= MRAFT_F_STEPPED_DOWN;
+  } else if (rt == term && role == kLeader && at == term && ap == nxp - 1) {  // :73-74
+    fl |= MRAFT_F_APPLIED;
+    touched_mn = true;
+    if (r(&R::reply_success)) {
+      const int mv = r(&R::args_n_entries) + ap;                         // :76
+      nxp = mv + 1;                                                      // :77
 #pragma unroll
-      for (int j = 0; j < P; ++j) if (j == pr) nxp = nx[j];
-      if (rt > term) {                                                   // :67-72
-        term = rt; role = kFollower;
-        fl |= MRAFT_F_STEPPED_DOWN;
-      } else if (rt == term && role == kLeader && at == term && ap == nxp - 1) {  // :73-74
-        fl |= MRAFT_F_APPLIED;
-        touched_mn = true;
-        if (__builtin_amdgcn_readlane(it.reply_success, k)) {
-          const int mv = __builtin_amdgcn_readlane(it.args_n_entries, k) + ap;  // :76
-          nxp = mv + 1;                                                  // :77
-#pragma unroll
-          for (int j = 0; j < P; ++j) if (j == pr) m[j] = mv;
-          const int top = min(quorum<P>(m, me), last);                // a1, :78
-          if (top > H) {
-            if (lane == k) { plo = H + 1; phi = top; }
-            H = top;
-          }
-        } else {
-          nxp = __builtin_amdgcn_readlane(it.reply_conflict_index, k);   // :82
-        }
-#pragma unroll
-        for (int j = 0; j < P; ++j) if (j == pr) nx[j] = nxp;
-        if (nxp < last + 1) fl |= MRAFT_F_NEED_MORE;                     // :84-86
+      for (int j = 0; j < P; ++j) if (j == pr) m[j] = mv;
+      const int top = min(quorum<P>(m, me), last);                       // a1, :78
+      if (top > H) {
+        if (ln == k) { plo = H + 1; phi = top; }
+        H = top;
       }
-      if (lane == k) myfl = fl;
+    } else {
+      nxp = r(&R::reply_conflict_index);                                 // :82
     }
-    // The batch's a1 ranges: probe every top word at once, scan the rest.
-    int x = -1;
-    bool settled = false;
-    if (plo <= phi) {
-      const int pv = lrow[ring(phi - dummy + head, s.L)];
-      if (pv == t0) x = phi;                                             // :98
-      else settled = srt && pv < t0;
-    }
-    unsigned long long pend = __ballot(plo < phi && x < 0 && !settled);
-    while (pend) {
-      const int src = first_lane(pend);
-      pend &= pend - 1;
-      const int lo = __shfl(plo, src, 64), hi = __shfl(phi, src, 64) - 1;
-      const int r = fold_scan_down_eq<kFoldScanU>(lrow, dummy, head, s.L, lo, hi, t0);  // lo - 1 if none
-      if (lane == src && r >= lo) x = r;
-    }
-    if (x >= 0) myfl |= MRAFT_F_COMMITTED;                               // :99-100
-    const unsigned long long fm = __ballot(x >= 0);
-    if (fm) commit = __shfl(x, 63 - __builtin_clzll(fm), 64);           // the latest range that found one
-    if (lane < nb) {
-      flags[b + base + lane] = myfl;
-      item_err[b + base + lane] = 0;
-    }
+#pragma unroll
+    for (int j = 0; j < P; ++j) if (j == pr) nx[j] = nxp;
+    if (nxp < last + 1) fl |= MRAFT_F_NEED_MORE;                         // :84-86
   }
-  if (term != t0 || role != r0) {
-    if (lane == 0) {
-      s.term[slot] = term; s.role[slot] = role; s.voted[slot] = -1;
-      mark_persist(s, slot, MRAFT_PERSIST_STATE);                        // :72
-    }
+  return fl;
+}
+
+// The top-word probe of this lane's a1 range (has: it holds one): on a log
+// whose last entries carry the current term every range ends at its top.
+// Returns phi when the top term is t0 (:98), else -1, and whether the range
+// stays open for a scan of [plo, phi - 1]. With sorted terms (include/mraft.h
+// MRAFT_TERMS_SORTED) a top term below currentTerm settles the range: no lower
+// entry carries currentTerm.
+__device__ __forceinline__ int a1_probe(bool has, const int32_t *__restrict__ lrow, int dummy, int head, int L,
+                                        int plo, int phi, int t0, int srt, bool &open) {
+  int x = -1;
+  bool settled = false;
+  if (has) {
+    const int pv = lrow[ring(phi - dummy + head, L)];
+    if (pv == t0) x = phi;
+    else settled = srt && pv < t0;
   }
-  if (commit != c0 && lane == 0) s.commit[slot] = commit;
+  open = has && plo < phi && x < 0 && !settled;
+  return x;
+}
+
+// :99-100 for the ranges whose index x the probes (and the long path's scans)
+// found: MRAFT_F_COMMITTED on the lane's reply, and commitIndex from the
+// latest range of the GW-lane group that found one.
+template <int GW>
+__device__ __forceinline__ void a1_commit(int x, int &myfl, int &commit) {
+  if (x >= 0) myfl |= MRAFT_F_COMMITTED;
+  const auto fm = gw_mask<GW>(x >= 0);
+  if (fm) commit = __shfl(x, gw_base<GW>() + last_lane(fm), 64);
+}
+
+// The segment's write-back: term, role, votedFor and the persist mark (:72)
+// and commitIndex by the segment's first lane, the match / next rows by its
+// peer lanes (pl: the lane's position among them).
+template <int P>
+__device__ __forceinline__ void fold_write_back(const Dev &s, int slot, int64_t mrow, bool first, bool peer_lane,
+                                                int pl, int term, int role, int commit, int t0, int r0, int c0,
+                                                bool touched_mn, const int (&m)[8], const int (&nx)[8]) {
+  if (first && (term != t0 || role != r0)) {
+    s.term[slot] = term; s.role[slot] = role; s.voted[slot] = -1;
+    mark_persist(s, slot, MRAFT_PERSIST_STATE);                          // :72
+  }
+  if (first && commit != c0) s.commit[slot] = commit;
   if (touched_mn) {
     int om = 0, on = 0;
 #pragma unroll
-    for (int j = 0; j < P; ++j) if (lane == j) { om = m[j]; on = nx[j]; }
-    if (lane < P) { s.match[mrow + lane] = om; s.next[mrow + lane] = on; }
+    for (int j = 0; j < P; ++j) if (pl == j) { om = m[j]; on = nx[j]; }
+    if (peer_lane) { s.match[mrow + pl] = om; s.next[mrow + pl] = on; }
   }
 }
 
@@ -321,7 +287,7 @@ __device__ __forceinline__ void fold_scan_blocks(const Dev &s, const int4 *__res
       const int klo = __builtin_amdgcn_readlane(lo, k), khi = __builtin_amdgcn_readlane(hi, k);
       const int kslot = __builtin_amdgcn_readlane(ra.z, k), kt0 = __builtin_amdgcn_readlane(ra.w, k);
       const int kd = __builtin_amdgcn_readlane(rb.x, k), kh = __builtin_amdgcn_readlane(rb.y, k);
-      const int x = fold_scan_down_eq<kFscanU>(s.log + (int64_t)kslot * L, kd, kh, L, klo, khi,
+      const int x = wave_scan_down_eq<kFscanU>(s.log + (int64_t)kslot * L, kd, kh, L, klo, khi,
                                                                      kt0);  // klo - 1 if none
       if (lane == k && x >= klo) {
         flags[rb.z] |= MRAFT_F_COMMITTED;                                // :99-100
@@ -331,21 +297,100 @@ __device__ __forceinline__ void fold_scan_blocks(const Dev &s, const int4 *__res
   }
 }
 
-// Lane groups of GW lanes (the wave as 64 / GW groups).
-template <int GW>
-__device__ __forceinline__ int gw_base() { return (int)(lane_id() & ~(unsigned)(GW - 1)); }
-template <int GW>
-__device__ __forceinline__ unsigned gw_mask(bool pred) {  // this lane's group's ballot, bit k = its lane k
-  return (unsigned)((__ballot(pred) >> gw_base<GW>()) & ((1ull << GW) - 1));
+// The long path (a segment of more replies than a lane group: k_fold_tail),
+// one segment per wave on wave-uniform values. Its own: the replica's state in
+// one load per lane over lanes 0..22; the replies in 64-reply batches, lane k
+// loading reply k of a batch, so a batch arrives in one round trip; and each
+// batch's open a1 ranges scanned in place, wave-cooperatively, at its end.
+template <int P>
+__device__ __forceinline__ void fold_segment(const Dev &s, const mraft_ae_result *__restrict__ items,
+                                             const int64_t *__restrict__ seg_begin, int64_t sg,
+                                             const int32_t *__restrict__ seg_err,
+                                             const unsigned long long *__restrict__ claim, uint32_t epoch,
+                                             int32_t *__restrict__ flags, int32_t *__restrict__ item_err) {
+  const int lane = lane_id();
+  int64_t b, e;
+  const bool any = segment_bounds(seg_begin, sg, b, e);
+  int bad = uni(seg_err[sg]);  // the claim verdict: a bad segment's slot may be out of range
+  if (!any) return;
+  const int64_t cnt = e - b;
+  mraft_ae_result it{};
+  if (lane < cnt) it = items[b + lane];
+  const int slot = __builtin_amdgcn_readfirstlane(it.slot);
+  const int me = slot % P;
+  const int64_t mrow = (int64_t)slot * P;
+  // lanes 0..P-1 matchIndex, 8..8+P-1 nextIndex, 16..22 the scalars
+  const int32_t *src = nullptr;
+  int64_t si = slot;
+  if (lane < P) { src = s.match; si = mrow + lane; }
+  else if (lane >= 8 && lane < 8 + P) { src = s.next; si = mrow + lane - 8; }
+  else if (lane == 16) src = s.term;
+  else if (lane == 17) src = s.role;
+  else if (lane == 18) src = s.commit;
+  else if (lane == 19) src = s.last;
+  else if (lane == 20) src = s.dummy;
+  else if (lane == 21) src = s.head;
+  else if (lane == 22) src = s.srt;
+  const int vs = (src && !bad) ? src[si] : 0;
+  const unsigned long long cw = !bad ? claim[slot] : 0ull;  // loaded beside the state
+  if (!bad && !claim_owned((uint32_t)uni((int)(uint32_t)cw), (uint32_t)(cw >> 32), epoch, sg)) bad = MRAFT_ITEM_DUP_SLOT;
+  int term = __builtin_amdgcn_readlane(vs, 16), role = __builtin_amdgcn_readlane(vs, 17),
+      commit = __builtin_amdgcn_readlane(vs, 18);
+  const int last = __builtin_amdgcn_readlane(vs, 19), dummy = __builtin_amdgcn_readlane(vs, 20),
+            head = __builtin_amdgcn_readlane(vs, 21), srt = __builtin_amdgcn_readlane(vs, 22);
+  bool malformed = false;
+  for (int64_t base = 0; base < cnt; base += 64) {
+    const int64_t i = base + lane;
+    if (__ballot(i < cnt && reply_malformed<P>(base > 0 ? items[b + i] : it, slot, me))) malformed = true;
+  }
+  bad = fold_verdict(bad, malformed, commit, dummy);
+  if (bad) {
+    for (int64_t i = lane; i < cnt; i += 64) { item_err[b + i] = bad; flags[b + i] = 0; }
+    return;
+  }
+  int m[8], nx[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    m[j] = j < P ? __builtin_amdgcn_readlane(vs, j) : 0;
+    nx[j] = j < P ? __builtin_amdgcn_readlane(vs, 8 + j) : 0;
+  }
+  const int c0 = commit, t0 = term, r0 = role;
+  const int32_t *lrow = s.log + (int64_t)slot * s.L;
+  bool touched_mn = false;
+  int H = commit;
+  for (int64_t base = 0; base < cnt; base += 64) {
+    if (base > 0 && base + lane < cnt) it = items[b + base + lane];
+    const int nb = (int)min((int64_t)64, cnt - base);
+    int myfl = 0, plo = 1, phi = 0;  // this lane's reply: flags and a1 range
+    for (int k = 0; k < nb; ++k) {
+      const int fl = reply_step<P>(LaneReply{it, k}, lane, k, term, role, m, nx, H, last, me, touched_mn, plo, phi);
+      if (lane == k) myfl = fl;
+    }
+    // The batch's a1 ranges: probe every top word at once, scan the rest.
+    bool open;
+    int x = a1_probe(plo <= phi, lrow, dummy, head, s.L, plo, phi, t0, srt, open);
+    for (unsigned long long pend = __ballot(open); pend; pend &= pend - 1) {
+      const int src = first_lane(pend);
+      const int lo = __shfl(plo, src, 64), hi = __shfl(phi, src, 64) - 1;
+      const int r = wave_scan_down_eq<kFoldScanU>(lrow, dummy, head, s.L, lo, hi, t0);  // lo - 1 if none
+      if (lane == src && r >= lo) x = r;
+    }
+    a1_commit<64>(x, myfl, commit);
+    if (lane < nb) {
+      flags[b + base + lane] = myfl;
+      item_err[b + base + lane] = 0;
+    }
+  }
+  fold_write_back<P>(s, slot, mrow, lane == 0, lane < P, lane, term, role, commit, t0, r0, c0, touched_mn, m, nx);
 }
-template <int GW>
-__device__ __forceinline__ int gw_bcast(int v, int k) { return __shfl(v, gw_base<GW>() + k, 64); }
 
-// fold_segment for 64 / GW segments at once, one per GW-lane group: the same
-// statements on per-group (not wave-uniform) values, so the segments' chains
-// of dependent loads (bounds -> replies -> replica state -> probes) overlap in
-// one wave. Only segments of at most GW replies: a wave whose segments include
-// a longer one folds them one by one on all 64 lanes.
+// The group path: 64 / GW segments at once, one per GW-lane group, on
+// per-group (not wave-uniform) values, so the segments' chains of dependent
+// loads (bounds -> replies -> replica state -> probes) overlap in one wave.
+// Its own: the replica's state in three loads per lane; no batches (only
+// segments of at most GW replies: a longer one goes to the long-segment list,
+// the open a1 ranges to the pending list by push_pending, both for
+// k_fold_tail); and the replies' address formed from an SGPR base (uni_ptr).
 template <int P, int GW>
 __device__ __forceinline__ void fold_groupw(const Dev &s, const mraft_ae_result *__restrict__ items,
                                             int64_t n_items, const int64_t *__restrict__ seg_begin, int64_t sg0,
@@ -361,8 +406,10 @@ __device__ __forceinline__ void fold_groupw(const Dev &s, const mraft_ae_result 
   int64_t b = 0, e = 0;
   int bad = 0;
   if (live) {
-    b = seg_begin ? seg_begin[sg] : sg;
-    e = seg_begin ? seg_begin[sg + 1] : sg + 1;
+    // (segment_bounds' two edges by value: through its reference arguments
+    // k_fold takes up to three more VGPRs and, for 7 and 8 peers, spills)
+    b = segment_edge(seg_begin, sg);
+    e = segment_edge(seg_begin, sg + 1);
     bad = seg_err[sg];  // the claim verdict: a bad segment's slot may be out of range
   }
   int cnt = (int)(e > b ? min(e - b, (int64_t)(GW + 1)) : 0);  // 0: nothing to fold (empty or inverted)
@@ -393,8 +440,7 @@ __device__ __forceinline__ void fold_groupw(const Dev &s, const mraft_ae_result 
   const int slot = gw_bcast<GW>(it.slot, 0);
   const int me = cnt ? slot % P : 0;
   const int64_t mrow = (int64_t)slot * P;
-  // The replica's state, three independent loads per lane: lanes 0..P-1 of
-  // the group matchIndex and nextIndex, lanes 0..5 the scalars.
+  // lanes 0..P-1 of the group matchIndex and nextIndex, lanes 0..6 the scalars
   int va = 0, vn = 0, vb = 0;
   if (cnt && !bad) {
     if (gl < P) {
@@ -405,19 +451,13 @@ __device__ __forceinline__ void fold_groupw(const Dev &s, const mraft_ae_result 
                          : gl == 4 ? s.dummy : gl == 5 ? s.head : gl == 6 ? s.srt : nullptr;
     if (src) vb = src[slot];
   }
-  // a slot claimed by an earlier segment of the batch: rejected (k_fold's check)
-  const unsigned long long cw = (cnt && !bad) ? claim[slot] : 0ull;
-  if (cnt && !bad && ((uint32_t)cw != (uint32_t)claim_tag(epoch, sg) || (uint32_t)(cw >> 32) != epoch))
-    bad = MRAFT_ITEM_DUP_SLOT;
+  const unsigned long long cw = (cnt && !bad) ? claim[slot] : 0ull;  // loaded beside the state
+  if (cnt && !bad && !claim_owned((uint32_t)cw, (uint32_t)(cw >> 32), epoch, sg)) bad = MRAFT_ITEM_DUP_SLOT;
   int term = gw_bcast<GW>(vb, 0), role = gw_bcast<GW>(vb, 1), commit = gw_bcast<GW>(vb, 2);
   const int last = gw_bcast<GW>(vb, 3), dummy = gw_bcast<GW>(vb, 4), head = gw_bcast<GW>(vb, 5);
   const int srt = gw_bcast<GW>(vb, 6);
-  // (a segment that does not own its slot stays MRAFT_ITEM_DUP_SLOT: the
-  // claim decides first, include/mraft.h)
-  if (gw_mask<GW>(gl < cnt && (it.slot != slot || it.peer < 0 || it.peer >= P || it.peer == me ||
-                               !reply_index_ok(it.args_prev_log_index, it.args_n_entries))) && !bad)
-    bad = MRAFT_ITEM_BAD_SLOT;
-  if (!bad && commit < dummy) bad = MRAFT_ITEM_BAD_STATE;
+  const bool malformed = gw_mask<GW>(gl < cnt && reply_malformed<P>(it, slot, me)) != 0;
+  bad = fold_verdict(bad, malformed, commit, dummy);
   if (bad) {
     if (gl < cnt) { item_err[b + gl] = bad; flags[b + gl] = 0; }
   }
@@ -437,75 +477,31 @@ __device__ __forceinline__ void fold_groupw(const Dev &s, const mraft_ae_result 
     if (__ballot(go && k < cnt)) nmax = k + 1;
   int myfl = 0, plo = 1, phi = 0;  // this lane's reply: flags and a1 range
   for (int k = 0; k < nmax; ++k) {
-    const int pr = gw_bcast<GW>(it.peer, k), rt = gw_bcast<GW>(it.reply_term, k);
-    const int at = gw_bcast<GW>(it.args_term, k), ap = gw_bcast<GW>(it.args_prev_log_index, k);
-    const int rs = gw_bcast<GW>(it.reply_success, k), rn = gw_bcast<GW>(it.args_n_entries, k);
-    const int rci = gw_bcast<GW>(it.reply_conflict_index, k);
+    HeldReply r{};  // reply k of each group
+    r.v.peer = gw_bcast<GW>(it.peer, k), r.v.reply_term = gw_bcast<GW>(it.reply_term, k);
+    r.v.args_term = gw_bcast<GW>(it.args_term, k), r.v.args_prev_log_index = gw_bcast<GW>(it.args_prev_log_index, k);
+    r.v.reply_success = gw_bcast<GW>(it.reply_success, k), r.v.args_n_entries = gw_bcast<GW>(it.args_n_entries, k);
+    r.v.reply_conflict_index = gw_bcast<GW>(it.reply_conflict_index, k);
     if (go && k < cnt) {
-      int fl = 0, nxp = 0;
-#pragma unroll
-      for (int j = 0; j < P; ++j) if (j == pr) nxp = nx[j];
-      if (rt > term) {                                                   // :67-72
-        term = rt; role = kFollower;
-        fl |= MRAFT_F_STEPPED_DOWN;
-      } else if (rt == term && role == kLeader && at == term && ap == nxp - 1) {  // :73-74
-        fl |= MRAFT_F_APPLIED;
-        touched_mn = true;
-        if (rs) {
-          const int mv = rn + ap;                                        // :76
-          nxp = mv + 1;                                                  // :77
-#pragma unroll
-          for (int j = 0; j < P; ++j) if (j == pr) m[j] = mv;
-          const int top = min(quorum<P>(m, me), last);                // a1, :78
-          if (top > H) {
-            if (gl == k) { plo = H + 1; phi = top; }
-            H = top;
-          }
-        } else {
-          nxp = rci;                                                     // :82
-        }
-#pragma unroll
-        for (int j = 0; j < P; ++j) if (j == pr) nx[j] = nxp;
-        if (nxp < last + 1) fl |= MRAFT_F_NEED_MORE;                     // :84-86
-      }
+      const int fl = reply_step<P>(r, gl, k, term, role, m, nx, H, last, me, touched_mn, plo, phi);
       if (gl == k) myfl = fl;
     }
   }
-  // a1's ranges of each group: every top word probed at once, the others scanned
-  // With sorted terms (include/mraft.h MRAFT_TERMS_SORTED) a top term below
-  // currentTerm settles the range: no lower entry carries currentTerm.
-  int x = -1;
-  bool settled = false;
-  if (go && plo <= phi) {
-    const int pv = lrow[ring(phi - dummy + head, s.L)];
-    if (pv == t0) x = phi;  // :98
-    else settled = srt && pv < t0;
-  }
-  // the ranges whose top word differs are scanned by k_fold_tail, after this
-  // launch: it ORs MRAFT_F_COMMITTED into the reply's flags and raises the
-  // replica's commitIndex to the highest index it finds (the ranges of a
-  // segment are disjoint and ascending, so "the latest range that found one"
-  // is the maximum over all of them, probes included)
-  push_pending(pend, pcount, go && plo + 1 <= phi && x < 0 && !settled, make_int4(plo, phi - 1, slot, t0),
-               make_int4(dummy, head, (int)(b + gl), 0));
-  if (go && x >= 0) myfl |= MRAFT_F_COMMITTED;                           // :99-100
-  const unsigned fm = gw_mask<GW>(go && x >= 0);
-  if (fm) commit = __shfl(x, gw_base<GW>() + 31 - __clz((int)fm), 64);   // the latest range that found one
+  // a1's ranges of each group: every top word probed at once. The ranges
+  // whose top word differs are scanned by k_fold_tail, after this launch: it
+  // ORs MRAFT_F_COMMITTED into the reply's flags and raises the replica's
+  // commitIndex to the highest index it finds (the ranges of a segment are
+  // disjoint and ascending, so "the latest range that found one" is the
+  // maximum over all of them, probes included).
+  bool open;
+  const int x = a1_probe(go && plo <= phi, lrow, dummy, head, s.L, plo, phi, t0, srt, open);
+  push_pending(pend, pcount, open, make_int4(plo, phi - 1, slot, t0), make_int4(dummy, head, (int)(b + gl), 0));
+  a1_commit<GW>(x, myfl, commit);
   if (go && gl < cnt) {
     flags[b + gl] = myfl;
     item_err[b + gl] = 0;
   }
-  if (go && gl == 0 && (term != t0 || role != r0)) {
-    s.term[slot] = term; s.role[slot] = role; s.voted[slot] = -1;
-    mark_persist(s, slot, MRAFT_PERSIST_STATE);                          // :72
-  }
-  if (go && gl == 0 && commit != c0) s.commit[slot] = commit;
-  if (go && touched_mn) {
-    int om = 0, on = 0;
-#pragma unroll
-    for (int j = 0; j < P; ++j) if (gl == j) { om = m[j]; on = nx[j]; }
-    if (gl < P) { s.match[mrow + gl] = om; s.next[mrow + gl] = on; }
-  }
+  fold_write_back<P>(s, slot, mrow, go && gl == 0, go && gl < P, gl, term, role, commit, t0, r0, c0, touched_mn, m, nx);
 }
 
 template <int P>

@@ -90,6 +90,7 @@ __device__ __forceinline__ Dev reload_dev() {
 // state stays live across the streaming pass; phase D recomputes each lane's
 // nextIndex / matchIndex from its own item. COUNT keeps the per-reply arrays
 // the algorithmic word count reads.
+// (The rule this restates in ballot-mask form: reply_step, mraft_fold.hip.)
 template <int P, bool COUNT>
 struct Fold {
   static constexpr int NI = P - 1;

@@ -50,8 +50,8 @@ from multiraft_amd.engine import copy_state, new_state  # noqa: E402
 GW = 8                      # replies a lane group folds; longer segments take the long path
 TOP = 2**31 - 2             # the highest Index of the engine's domain
 IMAX = 2**31 - 1
-SCAN_GROUP = (0, 1, 62, 63, 64, 65, 510, 511, 512, 513, 1023, 1024, 1025)   # around fold_scan_down_eq<8>'s 512
-SCAN_LONG = (0, 1, 62, 63, 64, 65, 254, 255, 256, 257, 511, 512, 513)       # around fold_scan_down_eq<4>'s 256
+SCAN_GROUP = (0, 1, 62, 63, 64, 65, 510, 511, 512, 513, 1023, 1024, 1025)   # around wave_scan_down_eq<8>'s 512
+SCAN_LONG = (0, 1, 62, 63, 64, 65, 254, 255, 256, 257, 511, 512, 513)       # around wave_scan_down_eq<4>'s 256
 RING0 = ("lo", "lo1", "mid", "hi1", "probe")
 
 
@@ -611,8 +611,8 @@ def _scan_group(gs, path, n, kind, j, T=5, dist_pad=3):
 
 def fam_scan(L):
     """E: both scans at capacity L. Group path: lengths and hit distances around
-    fold_scan_down_eq<8>'s 512 terms per iteration; long path: around
-    fold_scan_down_eq<4>'s 256; both 0, 1, 62..65. Per value: the range of that
+    wave_scan_down_eq<8>'s 512 terms per iteration; long path: around
+    wave_scan_down_eq<4>'s 256; both 0, 1, 62..65. Per value: the range of that
     length with its only hit at lo, the miss over that length, the hit at that
     distance below hi - 1."""
     gs = Groups(3, L)
