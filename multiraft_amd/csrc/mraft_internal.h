@@ -22,10 +22,6 @@ inline int blocks_for(int64_t n, int per_block = 256) {
   int64_t b = (n + per_block - 1) / per_block;
   return (int)(b < 1 ? 1 : b);
 }
-// The same for a kernel whose threads grid-stride over the items: at most
-// 4,096 workgroups.
-inline int blocks_strided(int64_t n, int per_block = 256) { return std::min(blocks_for(n, per_block), 4096); }
-
 // The kernels templated on the group size P: f(std::integral_constant<int, P>{})
 // for a runtime P in [Lo, 8]; false, with f not called, outside it.
 template <int Lo, class F>

@@ -15,6 +15,18 @@ namespace {
 
 constexpr int kBlock = 256;
 
+// Workgroups of the four kernels here whose threads grid-stride over the slots
+// (k_init_state, k_collect_apply, k_collect_persist: at most 4,096;
+// k_terms_sorted, a wave per slot: at most 65,536). MRAFT_STRIDED_GRID caps
+// them further: the small-grid test library compiles this unit with 1, so the
+// stride loops run their later passes on a small engine. Host code only.
+#ifndef MRAFT_STRIDED_GRID
+#define MRAFT_STRIDED_GRID (1 << 30)
+#endif
+int strided_grid(int64_t n, int cap = 4096) {
+  return std::min(blocks_for(n, kBlock), std::min(cap, (int)MRAFT_STRIDED_GRID));
+}
+
 // ---------------------------------------------------------------- Make
 __global__ void k_init_state(Dev s) {
   const int64_t gp = (int64_t)s.G * s.P;
@@ -528,13 +540,11 @@ void launch_items(K k, int64_t n, hipStream_t st, A... a) {
 
 void launch_terms_sorted(const Dev &s, hipStream_t st) {
   const int64_t gp = (int64_t)s.G * s.P;
-  int blocks = blocks_for(gp * 64);
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(k_terms_sorted, dim3(blocks), dim3(kBlock), 0, st, s);
+  hipLaunchKernelGGL(k_terms_sorted, dim3(strided_grid(gp * 64, 65536)), dim3(kBlock), 0, st, s);
 }
 
 void launch_init_state(const Dev &s, hipStream_t st) {
-  hipLaunchKernelGGL(k_init_state, dim3(blocks_strided((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s);
+  hipLaunchKernelGGL(k_init_state, dim3(strided_grid((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s);
 }
 
 void launch_claim(const void *items, int64_t n, int stride, int slot_off, const int64_t *seg_begin, int64_t gp,
@@ -561,7 +571,7 @@ void launch_start_groups(const Dev &s, const int32_t *lpeer, const StartIO &sio,
 
 void launch_collect_apply(const Dev &s, int32_t *from, int32_t *to, int32_t *snap_index, int32_t *snap_term,
                           hipStream_t st) {
-  hipLaunchKernelGGL(k_collect_apply, dim3(blocks_strided((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s, from, to,
+  hipLaunchKernelGGL(k_collect_apply, dim3(strided_grid((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s, from, to,
                      snap_index, snap_term);
 }
 
@@ -616,7 +626,7 @@ void launch_tally(const Dev &s, const mraft_rv_result *items, const int64_t *seg
 }
 
 void launch_collect_persist(const Dev &s, int32_t *out, hipStream_t st) {
-  hipLaunchKernelGGL(k_collect_persist, dim3(blocks_strided((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s, out);
+  hipLaunchKernelGGL(k_collect_persist, dim3(strided_grid((int64_t)s.G * s.P)), dim3(kBlock), 0, st, s, out);
 }
 
 void launch_read_persistent_hdr(const Dev &s, const int32_t *slots, int64_t n, mraft_persistent *out, hipStream_t st) {
