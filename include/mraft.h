@@ -385,7 +385,17 @@ int mraft_gather_append_args(mraft_engine *h, const int32_t *slots,
  * without waiting either). n <= 2^31 - 1.
  * Staged entries use the engine's stage (mraft_set_stage_capacity); a batch
  * that needs more runs its deferred items in an order that needs no stage
- * (slower), with the same results. */
+ * (slower), with the same results.
+ * Malformed items (MRAFT_ITEM_BAD_SLOT, no state change, a zero reply): a
+ * slot outside [0, G*P); n_entries < 0; entries_offset < 0; a last Index
+ * prev_log_index + n_entries past the Index domain. By value, n_entries > 0
+ * with entries_offset + n_entries > n_entry_terms (a heartbeat's offset is
+ * never used). By reference the offset names a position of the engine's log
+ * image and must lie in [0, G*P*L] whatever the count — a heartbeat's too,
+ * whose offset from the gather is at most (slot + 1) * L —:
+ * entries_offset + n_entries > G*P*L, or entries that run past their row,
+ * entries_offset % L + n_entries > L. A later item addressed to a slot an
+ * earlier one names (well-formed or not) is MRAFT_ITEM_DUP_SLOT. */
 int mraft_handle_append_entries(mraft_engine *h, const mraft_ae_args *args,
                                 int64_t n, const int32_t *entry_terms,
                                 int64_t n_entry_terms, mraft_ae_reply *replies,

@@ -87,7 +87,13 @@ enum ScratchSlot {
 // steps, up to 2^31 - 1 words (8 GiB).
 constexpr int64_t kStageStep = (int64_t)1 << 20;
 // Words of the fallback's per-workgroup cycle buffers (nslot x L, at most this).
-constexpr int64_t kCycSlotWords = (int64_t)1 << 25;  // 8,192 buffers at L = 4,096 (128 MiB)
+// A host constant (the kernels take nslot as an argument); the small-grid test
+// library sets it to 128, so at L = 64 two workgroups have a buffer and the
+// rest of the deferred grid only counts out.
+#ifndef MRAFT_CYC_SLOT_WORDS
+#define MRAFT_CYC_SLOT_WORDS ((int64_t)1 << 25)  // 8,192 buffers at L = 4,096 (128 MiB)
+#endif
+constexpr int64_t kCycSlotWords = MRAFT_CYC_SLOT_WORDS;
 
 struct mraft_engine {
   int32_t G = 0, P = 0, L = 0, device = 0;

@@ -302,7 +302,11 @@ __device__ __forceinline__ void handle_one(const HsArgs &k0, int64_t first, int 
       sm = k0.srcmark[f];
       if (ok && nn > 0) cr = k0.claim[srow];
     }
-    if (ok) rhead = s.head[srow];
+    // (the offset may name the end of the log image: (slot + 1) L, the heartbeat
+    // of a full-log leader at the last slot. srow = G P then: no row, no head.
+    // Any other heartbeat's head is needed: it may be the first merging member
+    // of a set, whose source every member's entries are read through)
+    if (ok && srow < gp) rhead = s.head[srow];
     if (MODE == HM_MAIN) {
       dup = !claim_won(cs, k0.epoch, i);
       dfr = !dup && ok && sm == k0.epoch;                              // `written`: deferred

@@ -255,6 +255,21 @@ static int ae_index_ok(const mraft_ae_args *a) {
   return (int64_t)a->prev_log_index + a->n_entries <= (int64_t)INT32_MAX - 1;
 }
 
+/* The malformed classes of an item (include/mraft.h,
+ * mraft_handle_append_entries): a negative count or offset, a last Index past
+ * the Index domain, entries that end past their buffer. By reference the
+ * offset names a position of the engine's log image, so it must lie in
+ * [0, G*P*L] whatever the count (a heartbeat's too: the gather's own
+ * heartbeats end at (slot + 1) * L at most), and the entries must not run past
+ * their row. By value the buffer bounds only the entries that exist: a
+ * heartbeat's offset is never used. */
+static int ae_wellformed(const mraft_ae_args *a, int by_ref, int64_t src_n, int32_t L) {
+  if (a->n_entries < 0 || a->entries_offset < 0 || !ae_index_ok(a)) return 0;
+  if (by_ref)
+    return a->entries_offset + a->n_entries <= src_n && a->entries_offset % L + a->n_entries <= L;
+  return a->n_entries == 0 || a->entries_offset + a->n_entries <= src_n;
+}
+
 /* ent = entries' terms (entry k has Index prev+1+k); cnt_src = the leader
  * replica whose log the entries were copied from (for counting its words), or
  * -1. */
@@ -386,10 +401,7 @@ int ora_handle_append_entries(ora_engine *e, const mraft_ae_args *args,
     for (int64_t i = 0; i < n; ++i) {
       const mraft_ae_args *a = &args[i];
       soff[i] = -1;
-      if (item_err[i] || a->n_entries < 0 || a->entries_offset < 0 || !ae_index_ok(a) ||
-          (a->n_entries > 0 && a->entries_offset + a->n_entries > src_n) ||
-          a->entries_offset % e->L + a->n_entries > e->L)
-        continue;
+      if (item_err[i] || !ae_wellformed(a, 1, src_n, e->L)) continue;
       soff[i] = tot;
       tot += a->n_entries;
     }
@@ -405,9 +417,7 @@ int ora_handle_append_entries(ora_engine *e, const mraft_ae_args *args,
     memset(&replies[i], 0, sizeof(replies[i]));
     if (item_err[i]) continue;
     const mraft_ae_args *a = &args[i];
-    if (a->n_entries < 0 || a->entries_offset < 0 || !ae_index_ok(a) ||
-        (a->n_entries > 0 && a->entries_offset + a->n_entries > src_n) ||
-        (!entry_terms && a->entries_offset % e->L + a->n_entries > e->L)) {
+    if (!ae_wellformed(a, !entry_terms, src_n, e->L)) {
       item_err[i] = MRAFT_ITEM_BAD_SLOT;
       continue;
     }

@@ -6,7 +6,11 @@ through mraft_handle_append_entries at the default stage, a stage too small
 each, the rest on the last workgroup), each twice on one engine: the first
 call on the minimal deferred grid (no earlier count: 512 workgroups, and 8
 through MRAFT_DEFER_GRID_MIN), the second on the grid the first call's count
-asked for. GPU == oracle (which copies every item's
+asked for. Every item of these batches is a successful merge at its own slot
+(message_cases.deferred_graph_batch), every workgroup has a cycle buffer and
+the graph shapes are the seed's: the other reply classes, the stage's boundary,
+placed graph shapes and workgroups without a buffer are
+tests/handler_cases.py's. GPU == oracle (which copies every item's
 entries before the call, as the reference's gather does,
 src/raft/raft_append_entry.go:50-54) on replies, errors and state."""
 import numpy as np
@@ -25,8 +29,10 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("shape", ["random", "long_cycle", "dense"])
 def test_deferred_graphs_gpu(shape, cap, gmin, monkeypatch):
     # gmin 8: the deferred launch's minimum grid far below the item count
-    # (MRAFT_DEFER_GRID_MIN, read at mraft_create): the grid-stride loops and,
-    # in the fallback, workgroups without a cycle buffer
+    # (MRAFT_DEFER_GRID_MIN, read at mraft_create): the grid-stride loops. At
+    # L = 64 every workgroup of either grid has a cycle buffer (2^25 / L far
+    # above the grid), so workgroups without one do not run here: they do in
+    # tests/test_handler_cases_gpu.py on the small-grid library
     if gmin is not None:
         monkeypatch.setenv("MRAFT_DEFER_GRID_MIN", str(gmin))
     G, P, L = 64, 5, 64
