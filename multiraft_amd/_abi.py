@@ -260,6 +260,20 @@ def ptr(a) -> int | None:
     raise TypeError(type(a))
 
 
+def to_words(records, device=None):
+    """A record array as a contiguous int32-word tensor [n, itemsize // 4] (a
+    copy), on `device` when one is given: the layout MRAFT_DEVICE batches take."""
+    import torch
+    a = np.ascontiguousarray(records)
+    t = torch.from_numpy(a.view(np.int32).reshape(len(a), a.dtype.itemsize // 4).copy())
+    return t if device is None else t.to(device)
+
+
+def from_words(words, dtype) -> np.ndarray:
+    """The inverse: a word tensor [n, itemsize // 4] as a host array of `dtype`."""
+    return np.ascontiguousarray(words.cpu().numpy()).view(dtype).reshape(-1)
+
+
 def soa_of(st: dict) -> MraftSoa:
     s = MraftSoa()
     for f in STATE_FIELDS:

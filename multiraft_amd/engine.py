@@ -17,6 +17,7 @@ import numpy as np
 from . import _abi
 from ._abi import (AE_ARGS, AE_REPLY, AE_RESULT, IS_ARGS, IS_REPLY, IS_RESULT, PERSISTENT, RV_ARGS,
                    RV_REPLY, RV_RESULT, DEVICE, HOST, STATE_FIELDS, ptr, soa_of)
+from ._calls import BatchCalls, _in, _outs
 
 
 class MraftError(RuntimeError):
@@ -107,8 +108,9 @@ def synth_fold_batch(st: dict, G: int, P: int, L: int, leader_peer: np.ndarray, 
     return items[:n], seg
 
 
-class Engine:
-    """One engine handle per GPU (calls must be serialized by the caller)."""
+class Engine(BatchCalls):
+    """One engine handle per GPU (calls must be serialized by the caller).
+    The batched message-path calls both libraries export are BatchCalls'."""
 
     def __init__(self, G: int, P: int, L: int, device: int = 0, alloc: bool = True,
                  dedicated_queue: bool = False):
@@ -118,6 +120,10 @@ class Engine:
         flags = (0 if alloc else _abi.CREATE_NO_ALLOC) | (_abi.CREATE_DEDICATED_QUEUE if dedicated_queue else 0)
         _ck(self._lib.mraft_create(G, P, L, device, flags, ctypes.byref(h)), "mraft_create")
         self._h = h
+
+    def _invoke(self, name, *c_args, where=HOST):
+        tail = () if where is None else (where,)
+        _ck(getattr(self._lib, "mraft_" + name)(self._h, *c_args, *tail), "mraft_" + name)
 
     # ---- lifetime --------------------------------------------------------
     def close(self):
@@ -265,68 +271,18 @@ class Engine:
             "mraft_replicate_tick_count")
         return int(out[0]), int(out[1]), int(out[2])
 
-    def gather_append_args(self, slots, peers):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        peers = np.ascontiguousarray(peers, dtype=np.int32)
-        n = len(slots)
-        out = np.zeros(n, dtype=AE_ARGS)
-        err = np.zeros(n, dtype=np.int32)
-        _ck(self._lib.mraft_gather_append_args(self._h, ptr(slots), ptr(peers), n, ptr(out),
-                                               ptr(err), HOST), "mraft_gather_append_args")
-        return out, err
-
-    def handle_append_entries(self, args: np.ndarray, entry_terms: np.ndarray | None, results: bool = False):
+    def handle_append_entries(self, args, entry_terms, results: bool = False, where: int = HOST, out=None,
+                              n=None):
         """HandleAppendEntries for a batch: (replies, item_err), and with
         results=True also the reply records the co-resident leaders fold
-        (mraft_handle_append_entries_ex)."""
-        args = np.ascontiguousarray(args, dtype=AE_ARGS)
-        n = len(args)
-        rep = np.zeros(n, dtype=AE_REPLY)
-        err = np.zeros(n, dtype=np.int32)
-        res = np.zeros(n, dtype=AE_RESULT) if results else None
-        et = None if entry_terms is None else np.ascontiguousarray(entry_terms, dtype=np.int32)
-        _ck(self._lib.mraft_handle_append_entries_ex(self._h, ptr(args), n, ptr(et),
-                                                     0 if et is None else len(et), ptr(rep), ptr(res),
-                                                     ptr(err), HOST), "mraft_handle_append_entries_ex")
+        (mraft_handle_append_entries_ex). where / out as in _calls; out is
+        (replies, results or None, item_err), the C order."""
+        args, et = _in(args, AE_ARGS, where), _in(entry_terms, np.int32, where)
+        n = len(args) if n is None else n
+        rep, res, err = _outs(out, (AE_REPLY, AE_RESULT if results else None, np.int32), n, where, args)
+        self._invoke("handle_append_entries_ex", ptr(args), n, ptr(et), 0 if et is None else len(et),
+                     ptr(rep), ptr(res), ptr(err), where=where)
         return (rep, err, res) if results else (rep, err)
-
-    def process_append_replies(self, items: np.ndarray, seg_begin: np.ndarray | None = None):
-        items = np.ascontiguousarray(items, dtype=AE_RESULT)
-        n = len(items)
-        flags = np.zeros(n, dtype=np.int32)
-        err = np.zeros(n, dtype=np.int32)
-        sb = None if seg_begin is None else np.ascontiguousarray(seg_begin, dtype=np.int64)
-        _ck(self._lib.mraft_process_append_replies(self._h, ptr(items), n, ptr(sb),
-                                                   0 if sb is None else len(sb) - 1, ptr(flags),
-                                                   ptr(err), HOST),
-            "mraft_process_append_replies")
-        return flags, err
-
-    def start(self, slots, counts=None):
-        """Start (raft.go:90-104): returns (index, term, is_leader, err)."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(slots)
-        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
-        idx = np.zeros(n, np.int32)
-        term = np.zeros(n, np.int32)
-        isl = np.zeros(n, np.int32)
-        err = np.zeros(n, np.int32)
-        _ck(self._lib.mraft_start(self._h, ptr(slots), ptr(c), n, ptr(idx), ptr(term), ptr(isl),
-                                  ptr(err), HOST), "mraft_start")
-        return idx, term, isl, err
-
-    def collect_apply(self, snapshots: bool = False):
-        """Applier (raft.go:153-203): per-slot ApplyMsg index ranges [from, to];
-        with snapshots=True also (snap_index, snap_term): the SnapshotValid
-        message each slot sends first (snap_index -1: none)."""
-        gp = self.G * self.P
-        fr = np.zeros(gp, np.int32)
-        to = np.zeros(gp, np.int32)
-        si = np.zeros(gp, np.int32) if snapshots else None
-        stm = np.zeros(gp, np.int32) if snapshots else None
-        _ck(self._lib.mraft_collect_apply(self._h, ptr(fr), ptr(to), ptr(si), ptr(stm), HOST),
-            "mraft_collect_apply")
-        return (fr, to, si, stm) if snapshots else (fr, to)
 
     def collect_apply_compact(self, cap: int | None = None, snapshots: bool = False):
         """Applier, compacted: (slots, from, to, total) for the slots with a
@@ -346,77 +302,6 @@ class Engine:
         if snapshots:
             return sl[:k].copy(), si[:k].copy(), stm[:k].copy(), fr[:k].copy(), to[:k].copy(), int(n[0])
         return sl[:k].copy(), fr[:k].copy(), to[:k].copy(), int(n[0])
-
-    # ---- snapshots (raft_snapshot.go) -------------------------------------
-    def snapshot(self, slots, index):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        index = np.ascontiguousarray(index, dtype=np.int32)
-        err = np.zeros(len(slots), np.int32)
-        _ck(self._lib.mraft_snapshot(self._h, ptr(slots), ptr(index), len(slots), ptr(err), HOST),
-            "mraft_snapshot")
-        return err
-
-    def gather_install_snapshot_args(self, slots, peers):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        peers = np.ascontiguousarray(peers, dtype=np.int32)
-        n = len(slots)
-        out = np.zeros(n, dtype=IS_ARGS)
-        err = np.zeros(n, np.int32)
-        _ck(self._lib.mraft_gather_install_snapshot_args(self._h, ptr(slots), ptr(peers), n, ptr(out),
-                                                         ptr(err), HOST),
-            "mraft_gather_install_snapshot_args")
-        return out, err
-
-    def handle_install_snapshot(self, args):
-        args = np.ascontiguousarray(args, dtype=IS_ARGS)
-        n = len(args)
-        rep = np.zeros(n, dtype=IS_REPLY)
-        fl = np.zeros(n, np.int32)
-        err = np.zeros(n, np.int32)
-        _ck(self._lib.mraft_handle_install_snapshot(self._h, ptr(args), n, ptr(rep), ptr(fl), ptr(err),
-                                                    HOST), "mraft_handle_install_snapshot")
-        return rep, fl, err
-
-    def process_install_snapshot_replies(self, items, seg_begin=None):
-        items = np.ascontiguousarray(items, dtype=IS_RESULT)
-        n = len(items)
-        fl = np.zeros(n, np.int32)
-        err = np.zeros(n, np.int32)
-        sb = None if seg_begin is None else np.ascontiguousarray(seg_begin, dtype=np.int64)
-        _ck(self._lib.mraft_process_install_snapshot_replies(
-            self._h, ptr(items), n, ptr(sb), 0 if sb is None else len(sb) - 1, ptr(fl), ptr(err), HOST),
-            "mraft_process_install_snapshot_replies")
-        return fl, err
-
-    # ---- elections -------------------------------------------------------
-    def start_election(self, slots):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(slots)
-        out = np.zeros(n, dtype=RV_ARGS)
-        err = np.zeros(n, dtype=np.int32)
-        _ck(self._lib.mraft_start_election(self._h, ptr(slots), n, ptr(out), ptr(err), HOST),
-            "mraft_start_election")
-        return out, err
-
-    def handle_request_vote(self, args: np.ndarray):
-        args = np.ascontiguousarray(args, dtype=RV_ARGS)
-        n = len(args)
-        rep = np.zeros(n, dtype=RV_REPLY)
-        err = np.zeros(n, dtype=np.int32)
-        _ck(self._lib.mraft_handle_request_vote(self._h, ptr(args), n, ptr(rep), ptr(err), HOST),
-            "mraft_handle_request_vote")
-        return rep, err
-
-    def process_vote_replies(self, items: np.ndarray, seg_begin: np.ndarray | None = None):
-        items = np.ascontiguousarray(items, dtype=RV_RESULT)
-        n = len(items)
-        flags = np.zeros(n, dtype=np.int32)
-        err = np.zeros(n, dtype=np.int32)
-        sb = None if seg_begin is None else np.ascontiguousarray(seg_begin, dtype=np.int64)
-        _ck(self._lib.mraft_process_vote_replies(self._h, ptr(items), n, ptr(sb),
-                                                 0 if sb is None else len(sb) - 1, ptr(flags),
-                                                 ptr(err), HOST), "mraft_process_vote_replies")
-        return flags, err
 
     def election_rounds(self, cand_mask, group_flags=None, where: int = HOST):
         """Election storm (config #5): len(cand_mask) rounds in one launch."""
@@ -529,46 +414,6 @@ class Engine:
         if rc < 0:
             _ck(rc, "mraft_get_reachable")
         return out if rc == 1 else None
-
-    # ---- persistence (raft.go:205-235) ------------------------------------
-    def collect_persist(self):
-        """persist_dirty of every slot (MRAFT_PERSIST_* bits), cleared on read."""
-        out = np.zeros(self.G * self.P, np.int32)
-        _ck(self._lib.mraft_collect_persist(self._h, ptr(out), HOST), "mraft_collect_persist")
-        return out
-
-    def read_persistent(self, slots):
-        """SaveState (raft.go:209-216) of the given slots: (PERSISTENT records,
-        packed log terms)."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(slots)
-        hdr = np.zeros(n, dtype=PERSISTENT)
-        if n == 0:
-            return hdr, np.zeros(0, np.int32)
-        cap = n * self.L
-        terms = np.zeros(cap, np.int32)
-        _ck(self._lib.mraft_read_persistent(self._h, ptr(slots), n, ptr(hdr), ptr(terms), cap),
-            "mraft_read_persistent")
-        used = int(hdr["terms_offset"][-1] + hdr["last_index"][-1] - hdr["dummy_index"][-1] + 1)
-        return hdr, terms[:used].copy()
-
-    def restore(self, hdr, terms):
-        """Crash + restart (Make + readPersist, raft.go:51-87,217-235)."""
-        hdr = np.ascontiguousarray(hdr, dtype=PERSISTENT)
-        terms = np.ascontiguousarray(terms, dtype=np.int32)
-        err = np.zeros(len(hdr), np.int32)
-        _ck(self._lib.mraft_restore(self._h, ptr(hdr), len(hdr), ptr(terms), len(terms), ptr(err)),
-            "mraft_restore")
-        return err
-
-    def export_group_status(self, leader_peer=None):
-        commit = np.zeros(self.G, dtype=np.int32)
-        tl = np.zeros(self.G, dtype=np.int32)
-        lp = None if leader_peer is None else np.ascontiguousarray(leader_peer, dtype=np.int32)
-        _ck(self._lib.mraft_export_group_status(self._h, ptr(lp), ptr(commit), ptr(tl), HOST),
-            "mraft_export_group_status")
-        return commit, tl
-
 
     # ---- multi-GPU fan-in (SURVEY.md §8e; include/mraft.h) -----------------
     def comm_init(self, nranks: int, rank: int, uid: bytes) -> int:

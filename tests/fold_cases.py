@@ -31,7 +31,6 @@ oracle, one JSON line {"cases": [[name, n_items, ok], ...]}, exit status 1 on
 any mismatch."""
 from __future__ import annotations
 
-import json
 import os
 import sys
 
@@ -42,6 +41,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 if os.path.dirname(HERE) not in sys.path:
     sys.path.insert(0, os.path.dirname(HERE))
+
+from cases_program import run_all, sorted_terms  # noqa: E402
 
 from multiraft_amd._abi import (AE_RESULT, CANDIDATE, F_APPLIED, F_COMMITTED, F_NEED_MORE,  # noqa: E402
                                 F_STEPPED_DOWN, FOLLOWER, ITEM_BAD_SLOT, ITEM_BAD_STATE, ITEM_DUP_SLOT, LEADER)
@@ -94,19 +95,6 @@ class Groups:
             st["next_index"][s * P:(s + 1) * P] = r["nx"]
         st["terms_sorted"] = sorted_terms(st, G, P, L)
         return st
-
-
-def sorted_terms(st: dict, G: int, P: int, L: int) -> np.ndarray:
-    """terms_sorted as mraft_load_state computes it: the terms of Index
-    dummy + 1 .. last never decrease."""
-    out = np.ones(G * P, np.int32)
-    for s in range(G * P):
-        n = int(st["last_index"][s] - st["dummy_index"][s])
-        if n >= 2:
-            row = st["log_term"][s * L:(s + 1) * L]
-            t = row[(int(st["log_head"][s]) + 1 + np.arange(n)) % L].astype(np.int64)
-            out[s] = int((t[1:] >= t[:-1]).all())
-    return out
 
 
 def rec(slot, peer, T, prev, n=0, ok=1, rt=None, ci=0):
@@ -988,16 +976,8 @@ def main():
     from oracle_lib import Oracle, assert_states_equal
 
     from multiraft_amd import Engine
-    out, bad = [], 0
-    for name, _, _ in FAMILIES:
-        try:
-            n, ok = run_family(name, Engine, Oracle, assert_states_equal), True
-        except AssertionError as ex:
-            print(f"{name}: {ex}", file=sys.stderr)
-            n, ok, bad = len(family(name)[4]), False, bad + 1
-        out.append([name, n, ok])
-    print(json.dumps({"cases": out}))
-    return 1 if bad else 0
+    return run_all([(n,) for n, _, _ in FAMILIES], lambda n: run_family(n, Engine, Oracle, assert_states_equal),
+                   lambda n: len(family(n)[4]))
 
 
 if __name__ == "__main__":

@@ -22,7 +22,6 @@ and stripe that serve an item, written / read (staged), the fallback's graph
 (writers, reader counts, cycles) and the staged words per stripe. `cells`
 names what a batch holds from `geometry` and the model's per-item record;
 tests/test_handler_cases.py proves every claimed cell present."""
-import json
 import os
 import sys
 
@@ -33,6 +32,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 if os.path.dirname(HERE) not in sys.path:
     sys.path.insert(0, os.path.dirname(HERE))
+
+from cases_program import run_all  # noqa: E402
 
 from multiraft_amd._abi import (AE_ARGS, AE_ENTRIES_SORTED, AE_REPLY, AE_RESULT, FOLLOWER, ITEM_BAD_SLOT,  # noqa: E402
                                 ITEM_DUP_SLOT, ITEM_LOG_FULL, LEADER, PERSIST_STATE)
@@ -1396,23 +1397,19 @@ def main():
     from oracle_lib import Oracle, assert_states_equal
 
     from multiraft_amd import Engine, _abi
-    out, bad = [], 0
-    for name in NAMES:
-        for cap, gmin in modes(name):
-            try:
-                k, ok = run_family(name, Engine, Oracle, assert_states_equal, cap, gmin), True
-            except AssertionError as ex:
-                print(f"{name} stage {cap} grid {gmin}: {ex}", file=sys.stderr)
-                k, ok, bad = 0, False, bad + 1
-            out.append([name, cap, gmin, k, ok])
-    viol = {}
-    for fn in ("mraft_debug_bounds_kernels", "mraft_debug_bounds_deferred", "mraft_debug_bounds_tick"):
-        f = getattr(_abi.lib(), fn, None)
-        if f is not None:
-            f.restype, f.argtypes = ctypes.c_longlong, [ctypes.c_int]
-            viol[fn] = int(f(0))
-    print(json.dumps({"cases": out, "violations": viol}))
-    return 1 if bad else 0
+
+    def violations():
+        viol = {}
+        for fn in ("mraft_debug_bounds_kernels", "mraft_debug_bounds_deferred", "mraft_debug_bounds_tick"):
+            f = getattr(_abi.lib(), fn, None)
+            if f is not None:
+                f.restype, f.argtypes = ctypes.c_longlong, [ctypes.c_int]
+                viol[fn] = int(f(0))
+        return {"violations": viol}
+
+    return run_all([(n, cap, gmin) for n in NAMES for cap, gmin in modes(n)],
+                   lambda n, cap, gmin: run_family(n, Engine, Oracle, assert_states_equal, cap, gmin),
+                   lambda *run: 0, violations)
 
 
 if __name__ == "__main__":

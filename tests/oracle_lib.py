@@ -7,8 +7,8 @@ import os
 
 import numpy as np
 
-from multiraft_amd._abi import (AE_ARGS, AE_REPLY, AE_RESULT, IS_ARGS, IS_REPLY, IS_RESULT,
-                                PERSISTENT, RV_ARGS, RV_REPLY, RV_RESULT, MraftSoa, ptr, soa_of)
+from multiraft_amd._abi import AE_ARGS, AE_REPLY, AE_RESULT, HOST, MraftSoa, ptr, soa_of
+from multiraft_amd._calls import BatchCalls
 from multiraft_amd.engine import copy_state
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,6 +20,41 @@ class OraEngine(ctypes.Structure):
                 ("s", MraftSoa)]
 
 
+_vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+_E = ctypes.POINTER(OraEngine)
+# argument types of every symbol used; the ora_<name> of a BatchCalls method has
+# mraft_<name>'s without the trailing `where` (tests/test_calls.py)
+SIGS = {
+    "ora_count_enable": [_E], "ora_count_disable": [], "ora_count_result": [_vp],
+    "ora_count_result_lines": [_i32, _vp],
+    "ora_compute_terms_sorted": [_E],
+    "ora_gather_append_args": [_E, _vp, _vp, _i64, _vp, _vp],
+    "ora_handle_append_entries": [_E, _vp, _i64, _vp, _i64, _vp, _vp],
+    "ora_process_append_replies": [_E, _vp, _i64, _vp, _i64, _vp, _vp],
+    "ora_replicate_tick": [_E, _vp, _vp],
+    "ora_replicate_tick_mt": [_E, _vp, _vp, _i32],
+    "ora_start": [_E, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "ora_collect_apply": [_E, _vp, _vp, _vp, _vp],
+    "ora_start_election": [_E, _vp, _i64, _vp, _vp],
+    "ora_handle_request_vote": [_E, _vp, _i64, _vp, _vp],
+    "ora_process_vote_replies": [_E, _vp, _i64, _vp, _i64, _vp, _vp],
+    "ora_export_group_status": [_E, _vp, _vp, _vp],
+    "ora_election_rounds": [_E, _vp, _i32, _vp],
+    "ora_election_rounds_mt": [_E, _vp, _i32, _vp, _i32],
+    "ora_snapshot": [_E, _vp, _vp, _i64, _vp],
+    "ora_gather_install_snapshot_args": [_E, _vp, _vp, _i64, _vp, _vp],
+    "ora_handle_install_snapshot": [_E, _vp, _i64, _vp, _vp, _vp],
+    "ora_process_install_snapshot_replies": [_E, _vp, _i64, _vp, _i64, _vp, _vp],
+    "ora_collect_persist": [_E, _vp],
+    "ora_read_persistent": [_E, _vp, _i64, _vp, _vp, _i64],
+    "ora_restore": [_E, _vp, _i64, _vp, _i64, _vp],
+    "goshape_build": [_i32, _i32, _i32, ctypes.POINTER(MraftSoa)],
+    "goshape_store": [_vp, ctypes.POINTER(MraftSoa)],
+    "goshape_free": [_vp],
+    "goshape_tick": [_vp, _vp, _i32],
+    "goshape_reset": [_vp, ctypes.POINTER(MraftSoa), _i32],
+}
+
 _lib = None
 
 
@@ -27,39 +62,7 @@ def lib():
     global _lib
     if _lib is None:
         l = ctypes.CDLL(_PATH)
-        vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
-        E = ctypes.POINTER(OraEngine)
-        sigs = {
-            "ora_count_enable": [E], "ora_count_disable": [], "ora_count_result": [vp],
-            "ora_count_result_lines": [i32, vp],
-            "ora_compute_terms_sorted": [E],
-            "ora_gather_append_args": [E, vp, vp, i64, vp, vp],
-            "ora_handle_append_entries": [E, vp, i64, vp, i64, vp, vp],
-            "ora_process_append_replies": [E, vp, i64, vp, i64, vp, vp],
-            "ora_replicate_tick": [E, vp, vp],
-            "ora_replicate_tick_mt": [E, vp, vp, i32],
-            "ora_start": [E, vp, vp, i64, vp, vp, vp, vp],
-            "ora_collect_apply": [E, vp, vp, vp, vp],
-            "ora_start_election": [E, vp, i64, vp, vp],
-            "ora_handle_request_vote": [E, vp, i64, vp, vp],
-            "ora_process_vote_replies": [E, vp, i64, vp, i64, vp, vp],
-            "ora_export_group_status": [E, vp, vp, vp],
-            "ora_election_rounds": [E, vp, i32, vp],
-            "ora_election_rounds_mt": [E, vp, i32, vp, i32],
-            "ora_snapshot": [E, vp, vp, i64, vp],
-            "ora_gather_install_snapshot_args": [E, vp, vp, i64, vp, vp],
-            "ora_handle_install_snapshot": [E, vp, i64, vp, vp, vp],
-            "ora_process_install_snapshot_replies": [E, vp, i64, vp, i64, vp, vp],
-            "ora_collect_persist": [E, vp],
-            "ora_read_persistent": [E, vp, i64, vp, vp, i64],
-            "ora_restore": [E, vp, i64, vp, i64, vp],
-            "goshape_build": [i32, i32, i32, ctypes.POINTER(MraftSoa)],
-            "goshape_store": [vp, ctypes.POINTER(MraftSoa)],
-            "goshape_free": [vp],
-            "goshape_tick": [vp, vp, i32],
-            "goshape_reset": [vp, ctypes.POINTER(MraftSoa), i32],
-        }
-        for n, a in sigs.items():
+        for n, a in SIGS.items():
             f = getattr(l, n)
             f.argtypes = a
             f.restype = None if n in ("ora_count_disable", "ora_count_result", "ora_count_result_lines", "goshape_store",
@@ -70,9 +73,10 @@ def lib():
     return _lib
 
 
-class Oracle:
-    """CPU restatement with the Engine's interface; operates on its own copy
-    of the state."""
+class Oracle(BatchCalls):
+    """CPU restatement with the Engine's interface (the batched message-path
+    calls are BatchCalls', host arrays only); operates on its own copy of the
+    state."""
 
     def __init__(self, G: int, P: int, L: int, st: dict):
         self.G, self.P, self.L = G, P, L
@@ -82,6 +86,12 @@ class Oracle:
         self.st["terms_sorted"] = np.zeros(G * P, np.int32)
         self._e = OraEngine(G, P, L, soa_of(self.st))
         lib().ora_compute_terms_sorted(ctypes.byref(self._e))  # as mraft_load_state does
+
+    def _invoke(self, name, *c_args, where=HOST):
+        if where not in (None, HOST):
+            raise ValueError(f"ora_{name}: the oracle takes host arrays only")
+        rc = getattr(lib(), "ora_" + name)(ctypes.byref(self._e), *c_args)
+        assert rc == 0, f"ora_{name} failed ({rc})"
 
     def state(self) -> dict:
         return self.st
@@ -125,50 +135,14 @@ class Oracle:
             return int(out[0]), int(out[1]), active, lines
         return int(out[0]), int(out[1]), active
 
-    def gather_append_args(self, slots, peers):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        peers = np.ascontiguousarray(peers, dtype=np.int32)
-        n = len(slots)
-        out = np.zeros(n, dtype=AE_ARGS)
-        err = np.zeros(n, dtype=np.int32)
-        lib().ora_gather_append_args(ctypes.byref(self._e), ptr(slots), ptr(peers), n, ptr(out), ptr(err))
-        return out, err
-
     def handle_append_entries(self, args, entry_terms):
         args = np.ascontiguousarray(args, dtype=AE_ARGS)
         n = len(args)
         rep = np.zeros(n, dtype=AE_REPLY)
         err = np.zeros(n, dtype=np.int32)
         et = None if entry_terms is None else np.ascontiguousarray(entry_terms, dtype=np.int32)
-        lib().ora_handle_append_entries(ctypes.byref(self._e), ptr(args), n, ptr(et),
-                                        0 if et is None else len(et), ptr(rep), ptr(err))
+        self._invoke("handle_append_entries", ptr(args), n, ptr(et), 0 if et is None else len(et), ptr(rep), ptr(err))
         return rep, err
-
-    def process_append_replies(self, items, seg_begin=None):
-        items = np.ascontiguousarray(items, dtype=AE_RESULT)
-        n = len(items)
-        flags = np.zeros(n, dtype=np.int32)
-        err = np.zeros(n, dtype=np.int32)
-        sb = None if seg_begin is None else np.ascontiguousarray(seg_begin, dtype=np.int64)
-        lib().ora_process_append_replies(ctypes.byref(self._e), ptr(items), n, ptr(sb),
-                                         0 if sb is None else len(sb) - 1, ptr(flags), ptr(err))
-        return flags, err
-
-    def start(self, slots, counts=None):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(slots)
-        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
-        idx, term, isl, err = (np.zeros(n, np.int32) for _ in range(4))
-        lib().ora_start(ctypes.byref(self._e), ptr(slots), ptr(c), n, ptr(idx), ptr(term), ptr(isl), ptr(err))
-        return idx, term, isl, err
-
-    def collect_apply(self, snapshots: bool = False):
-        gp = self.G * self.P
-        fr, to = np.zeros(gp, np.int32), np.zeros(gp, np.int32)
-        si = np.zeros(gp, np.int32) if snapshots else None
-        stm = np.zeros(gp, np.int32) if snapshots else None
-        lib().ora_collect_apply(ctypes.byref(self._e), ptr(fr), ptr(to), ptr(si), ptr(stm))
-        return (fr, to, si, stm) if snapshots else (fr, to)
 
     def store_state(self):
         return copy_state(self.st)
@@ -177,104 +151,11 @@ class Oracle:
         """The live state arrays (read-only use: the harness's mirror)."""
         return self.st
 
-    # ---- snapshots ---------------------------------------------------------
-    def snapshot(self, slots, index):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        index = np.ascontiguousarray(index, dtype=np.int32)
-        err = np.zeros(len(slots), np.int32)
-        lib().ora_snapshot(ctypes.byref(self._e), ptr(slots), ptr(index), len(slots), ptr(err))
-        return err
-
-    def gather_install_snapshot_args(self, slots, peers):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        peers = np.ascontiguousarray(peers, dtype=np.int32)
-        n = len(slots)
-        out = np.zeros(n, dtype=IS_ARGS)
-        err = np.zeros(n, np.int32)
-        lib().ora_gather_install_snapshot_args(ctypes.byref(self._e), ptr(slots), ptr(peers), n, ptr(out), ptr(err))
-        return out, err
-
-    def handle_install_snapshot(self, args):
-        args = np.ascontiguousarray(args, dtype=IS_ARGS)
-        n = len(args)
-        rep = np.zeros(n, dtype=IS_REPLY)
-        fl = np.zeros(n, np.int32)
-        err = np.zeros(n, np.int32)
-        lib().ora_handle_install_snapshot(ctypes.byref(self._e), ptr(args), n, ptr(rep), ptr(fl), ptr(err))
-        return rep, fl, err
-
-    def process_install_snapshot_replies(self, items, seg_begin=None):
-        items = np.ascontiguousarray(items, dtype=IS_RESULT)
-        n = len(items)
-        fl = np.zeros(n, np.int32)
-        err = np.zeros(n, np.int32)
-        sb = None if seg_begin is None else np.ascontiguousarray(seg_begin, dtype=np.int64)
-        lib().ora_process_install_snapshot_replies(ctypes.byref(self._e), ptr(items), n, ptr(sb),
-                                                   0 if sb is None else len(sb) - 1, ptr(fl), ptr(err))
-        return fl, err
-
-    def start_election(self, slots):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(slots)
-        out = np.zeros(n, dtype=RV_ARGS)
-        err = np.zeros(n, dtype=np.int32)
-        lib().ora_start_election(ctypes.byref(self._e), ptr(slots), n, ptr(out), ptr(err))
-        return out, err
-
-    def handle_request_vote(self, args):
-        args = np.ascontiguousarray(args, dtype=RV_ARGS)
-        n = len(args)
-        rep = np.zeros(n, dtype=RV_REPLY)
-        err = np.zeros(n, dtype=np.int32)
-        lib().ora_handle_request_vote(ctypes.byref(self._e), ptr(args), n, ptr(rep), ptr(err))
-        return rep, err
-
-    def process_vote_replies(self, items, seg_begin=None):
-        items = np.ascontiguousarray(items, dtype=RV_RESULT)
-        n = len(items)
-        flags = np.zeros(n, dtype=np.int32)
-        err = np.zeros(n, dtype=np.int32)
-        sb = None if seg_begin is None else np.ascontiguousarray(seg_begin, dtype=np.int64)
-        lib().ora_process_vote_replies(ctypes.byref(self._e), ptr(items), n, ptr(sb),
-                                       0 if sb is None else len(sb) - 1, ptr(flags), ptr(err))
-        return flags, err
-
     def election_rounds(self, cand_mask, nthreads: int = 1):
         m = np.ascontiguousarray(cand_mask, dtype=np.uint8)
         gf = np.zeros(self.G, np.int32)
         lib().ora_election_rounds_mt(ctypes.byref(self._e), ptr(m), m.shape[0], ptr(gf), nthreads)
         return gf
-
-    # ---- persistence ---------------------------------------------------------
-    def collect_persist(self):
-        out = np.zeros(self.G * self.P, np.int32)
-        lib().ora_collect_persist(ctypes.byref(self._e), ptr(out))
-        return out
-
-    def read_persistent(self, slots):
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(slots)
-        hdr = np.zeros(n, dtype=PERSISTENT)
-        cap = max(1, n * self.L)
-        terms = np.zeros(cap, np.int32)
-        rc = lib().ora_read_persistent(ctypes.byref(self._e), ptr(slots), n, ptr(hdr), ptr(terms), cap)
-        assert rc == 0
-        used = int((hdr["last_index"] - hdr["dummy_index"] + 1).sum()) if n else 0
-        return hdr, terms[:used].copy()
-
-    def restore(self, hdr, terms):
-        hdr = np.ascontiguousarray(hdr, dtype=PERSISTENT)
-        terms = np.ascontiguousarray(terms, dtype=np.int32)
-        err = np.zeros(len(hdr), np.int32)
-        lib().ora_restore(ctypes.byref(self._e), ptr(hdr), len(hdr), ptr(terms), len(terms), ptr(err))
-        return err
-
-    def export_group_status(self, leader_peer=None):
-        commit = np.zeros(self.G, dtype=np.int32)
-        tl = np.zeros(self.G, dtype=np.int32)
-        lp = None if leader_peer is None else np.ascontiguousarray(leader_peer, dtype=np.int32)
-        lib().ora_export_group_status(ctypes.byref(self._e), ptr(lp), ptr(commit), ptr(tl))
-        return commit, tl
 
 
 def logical_logs(st: dict, G: int, P: int, L: int):

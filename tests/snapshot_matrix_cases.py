@@ -34,7 +34,6 @@ any mismatch."""
 from __future__ import annotations
 
 import ctypes
-import json
 import os
 import sys
 
@@ -45,6 +44,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 if os.path.dirname(HERE) not in sys.path:
     sys.path.insert(0, os.path.dirname(HERE))
+
+from cases_program import run_all, sorted_terms  # noqa: E402
 
 from multiraft_amd import _abi  # noqa: E402
 from multiraft_amd._abi import (AE_ARGS, AE_ENTRIES_SORTED, CANDIDATE, E_INVAL, F_APPLIED,  # noqa: E402
@@ -111,18 +112,6 @@ class Reps:
                     st["next_index"][s * P + j] = r["nxt"].get(j, r["last"] + 1 if r["role"] == LEADER else 0)
         st["terms_sorted"] = sorted_terms(st, G, P, L)
         return st
-
-
-def sorted_terms(st: dict, G: int, P: int, L: int) -> np.ndarray:
-    """terms_sorted as mraft_load_state computes it."""
-    out = np.ones(G * P, np.int32)
-    for s in range(G * P):
-        n = int(st["last_index"][s] - st["dummy_index"][s])
-        if n >= 2:
-            row = st["log_term"][s * L:(s + 1) * L]
-            t = row[(int(st["log_head"][s]) + 1 + np.arange(n)) % L].astype(np.int64)
-            out[s] = int((t[1:] >= t[:-1]).all())
-    return out
 
 
 def is_items(recs):
@@ -528,27 +517,20 @@ class Model:
         return err
 
 
-# ---------------------------------------------------------------- calls the wrappers do not offer
-def handle_is_raw(eng, args, err_in):
+# ---------------------------------------------------------------- script steps per kind of object
+def handle_is_prefilled(eng, args, err_in):
     """HandleInstallSnapshot with the caller's item_err array as it stands
-    (the wrappers pass zeros): (replies, flags, item_err)."""
+    (out=; allocated outputs are zeros): (replies, flags, item_err)."""
     if isinstance(eng, Model):
         return eng.handle_install_snapshot(args, err_in)
-    args = np.ascontiguousarray(args, IS_ARGS)
     n = len(args)
-    rep, fl, err = np.zeros(n, IS_REPLY), np.zeros(n, np.int32), np.array(err_in, np.int32)
-    if hasattr(eng, "_h"):
-        rc = _abi.lib().mraft_handle_install_snapshot(eng._h, ptr(args), n, ptr(rep), ptr(fl), ptr(err), _abi.HOST)
-    else:
-        import oracle_lib
-        rc = oracle_lib.lib().ora_handle_install_snapshot(ctypes.byref(eng._e), ptr(args), n, ptr(rep), ptr(fl),
-                                                          ptr(err))
-    assert rc == 0
-    return rep, fl, err
+    return eng.handle_install_snapshot(args, out=(np.zeros(n, IS_REPLY), np.zeros(n, np.int32),
+                                                  np.array(err_in, np.int32)))
 
 
 def read_persistent_raw(eng, slots, cap):
-    """mraft_read_persistent with a chosen terms_cap: (rc, headers, terms)."""
+    """mraft_read_persistent with a chosen terms_cap, raw because the rc of a
+    cap one short is an output: (rc, headers, terms)."""
     if isinstance(eng, Model):
         return eng.read_persistent_raw(slots, cap)
     slots = np.ascontiguousarray(slots, np.int32)
@@ -649,7 +631,7 @@ def script_gather(eng, b, tick=True):
 def script_handle(eng, b, tick=True):
     """The batch, the applier without the snapshot outputs, then the compacted
     one with them, twice each; the follow-up; the applier with them."""
-    out = list(handle_is_raw(eng, b["args"], b["err_in"])) + [image(eng)]
+    out = list(handle_is_prefilled(eng, b["args"], b["err_in"])) + [image(eng)]
     out += list(eng.collect_apply()) + list(eng.collect_apply()) + [image(eng)]
     out += list(compact_of(eng, True)) + list(compact_of(eng, True)) + [image(eng)]
     out += list(eng.handle_install_snapshot(followup_handle(b))) + [image(eng)]
@@ -663,7 +645,7 @@ def script_handle_snap(eng, b, tick=True):
     """The same batch on an engine of its own, the appliers the other way
     round: mraft_collect_apply with the snapshot outputs straight after the
     batch, twice, then without them; after the follow-up the compacted one."""
-    out = list(handle_is_raw(eng, b["args"], b["err_in"])) + [image(eng)]
+    out = list(handle_is_prefilled(eng, b["args"], b["err_in"])) + [image(eng)]
     out += list(eng.collect_apply(snapshots=True)) + list(eng.collect_apply(snapshots=True)) + [image(eng)]
     out += list(eng.collect_apply()) + list(eng.collect_apply())
     out += list(eng.handle_install_snapshot(followup_handle(b))) + [image(eng)]
@@ -1590,16 +1572,7 @@ def main():
     from oracle_lib import Oracle, assert_states_equal
 
     from multiraft_amd import Engine
-    out, bad = [], 0
-    for name in NAMES:
-        try:
-            n, ok = run_family(name, Engine, Oracle, assert_states_equal), True
-        except AssertionError as ex:
-            print(f"{name}: {ex}", file=sys.stderr)
-            n, ok, bad = n_items(name), False, bad + 1
-        out.append([name, n, ok])
-    print(json.dumps({"cases": out}))
-    return 1 if bad else 0
+    return run_all([(n,) for n in NAMES], lambda n: run_family(n, Engine, Oracle, assert_states_equal), n_items)
 
 
 if __name__ == "__main__":

@@ -8,12 +8,11 @@ A subprocess runs every Index-domain case (tests/index_domain_cases.py: the
 tick and the message path through host buffers, in place, deferred, staged
 and the ordered fallback, at the top of the Index domain and at ordinary
 Indexes) on that library, GPU == oracle, and must report no violation."""
-import json
 import os
-import subprocess
-import sys
 
 import pytest
+
+from gpu_support import run_cases_child
 
 pytestmark = pytest.mark.gpu
 
@@ -22,12 +21,7 @@ DBG = os.path.join(ROOT, "multiraft_amd", "libmraft_hip_dbg.so")
 
 
 def test_no_ring_offset_out_of_range_gpu():
-    assert os.path.exists(DBG), "build() makes the bounds-checking library"
-    env = dict(os.environ, MRAFT_LIB=DBG)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "index_domain_cases.py")], env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_cases_child(os.path.join(ROOT, "tests", "index_domain_cases.py"), DBG)
     assert len(out["cases"]) >= 12 and all(c[-1] > 0 for c in out["cases"]), out["cases"]
     assert out["violations"] == {"mraft_debug_bounds_kernels": 0, "mraft_debug_bounds_deferred": 0,
                                  "mraft_debug_bounds_tick": 0}, out

@@ -8,19 +8,17 @@ device-resident batch buffers, two calls back to back without a host wait; and
 every family in a child process on the small-grid library
 (multiraft_amd/libmraft_hip_grid1.so: the fold's three grids at one workgroup,
 so k_fold's stride loop and both loops of k_fold_tail run)."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import fold_cases as fc
+from gpu_support import behind_spin, run_cases_child
 from oracle_lib import Oracle, assert_states_equal
 
-from multiraft_amd import DEVICE, Engine, _abi
-from multiraft_amd._abi import AE_RESULT
+from multiraft_amd import DEVICE, Engine
+from multiraft_amd._abi import AE_RESULT, to_words
 
 pytestmark = pytest.mark.gpu
 
@@ -71,24 +69,14 @@ def test_device_buffers_back_to_back_gpu(name):
     batches = [(items, seg), fc.followup(name, o.state(), G, P, L, fc.leader_peers(st, G, P))]
     want.append(o.process_append_replies(*batches[1]))
     dev = torch.device("cuda", 0)
-    lib = _abi.lib()
-    bufs = []
-    for it, sg in batches:
-        it_d = torch.from_numpy(np.ascontiguousarray(it, dtype=AE_RESULT).view(np.int32).reshape(-1, 8).copy()).to(dev)
-        bufs.append((it_d, torch.from_numpy(np.ascontiguousarray(sg, np.int64)).to(dev),
-                     torch.full((len(it),), -1, dtype=torch.int32, device=dev),
-                     torch.full((len(it),), -1, dtype=torch.int32, device=dev)))
+    fill = lambda n: torch.full((n,), -1, dtype=torch.int32, device=dev)  # noqa: E731
+    bufs = [(to_words(np.asarray(it, AE_RESULT), dev), torch.from_numpy(np.ascontiguousarray(sg, np.int64)).to(dev),
+             fill(len(it)), fill(len(it))) for it, sg in batches]
     with Engine(G, P, L) as e:
         e.load_state(st)
-        stream = torch.cuda.ExternalStream(e.stream(), device=dev)
-        e.synchronize()
-        with torch.cuda.stream(stream):
-            torch.cuda._sleep(int(1e8))  # device spin ahead of the calls
-        for (it, sg), (it_d, sg_d, fl_d, err_d) in zip(batches, bufs):
-            assert lib.mraft_process_append_replies(e._h, it_d.data_ptr(), len(it), sg_d.data_ptr(), len(sg) - 1,
-                                                    fl_d.data_ptr(), err_d.data_ptr(), DEVICE) == 0, _abi.last_error()
-        assert not stream.query(), "a fold call waited on the device"
-        e.synchronize()
+        with behind_spin(e, what="a fold call"):
+            for it_d, sg_d, fl_d, err_d in bufs:
+                e.process_append_replies(it_d, sg_d, where=DEVICE, out=(fl_d, err_d))
         got = e.store_state()
     for k, ((of, oerr), (_, _, fl_d, err_d)) in enumerate(zip(want, bufs)):
         assert np.array_equal(err_d.cpu().numpy(), oerr) and np.array_equal(fl_d.cpu().numpy(), of), (name, k)
@@ -98,12 +86,6 @@ def test_device_buffers_back_to_back_gpu(name):
 def test_small_grid_library_child_gpu():
     """Every family in a fresh process on the small-grid library: all ok, and
     the whole list ran."""
-    assert os.path.exists(GRID1), "build() makes the small-grid library"
-    env = dict(os.environ, MRAFT_LIB=GRID1)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fold_cases.py")], env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert r.stdout.strip(), r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_cases_child(os.path.join(ROOT, "tests", "fold_cases.py"), GRID1)
     assert [c[0] for c in out["cases"]] == NAMES, out["cases"]
-    assert all(c[2] is True and c[1] == len(fc.family(c[0])[4]) for c in out["cases"]), (out["cases"], r.stderr[-3000:])
-    assert r.returncode == 0, r.stderr[-3000:]
+    assert all(c[2] is True and c[1] == len(fc.family(c[0])[4]) for c in out["cases"]), out["cases"]

@@ -15,72 +15,77 @@ are ordered on the device (include/mraft.h, mraft_handle_ae.h "a4").
 import numpy as np
 import pytest
 
+from gpu_support import behind_spin
 from message_cases import all_follower_items, results_of, stale_cycle_state, stale_second_leader_state
 from oracle_lib import Oracle, assert_states_equal
 
 from multiraft_amd import DEVICE, Engine, _abi, synth_seed, synth_tick_state
-from multiraft_amd._abi import AE_ARGS, AE_REPLY, AE_RESULT
+from multiraft_amd._abi import AE_ARGS, AE_REPLY, AE_RESULT, from_words
 
 pytestmark = pytest.mark.gpu
+
+
+class Step:
+    """One message step's batch (every follower of the leaders in `lp`) and
+    its zeroed output buffers, all device-resident."""
+
+    def __init__(self, lp, G, P, dev):
+        import torch
+        self.slots, self.peers = all_follower_items(lp, G, P)
+        self.n = n = len(self.slots)
+        self.seg = np.concatenate([[0], np.cumsum(np.bincount(self.slots // P, minlength=G)[lp >= 0])]).astype(np.int64)
+        self.sl, self.pe, self.sg = (torch.from_numpy(a).to(dev) for a in (self.slots, self.peers, self.seg))
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        self.args, self.rep, self.res = z(n, 10), z(n, 4), z(n, 8)
+        self.gerr, self.herr, self.ferr, self.flags = z(n), z(n), z(n), z(n)
+
+    def enqueue(self, e, flags=None):
+        """gather -> handle -> fold on the device buffers; nothing waits."""
+        e.gather_append_args(self.sl, self.pe, where=DEVICE, out=(self.args, self.gerr))
+        e.handle_append_entries(self.args, None, results=True, where=DEVICE, out=(self.rep, self.res, self.herr))
+        e.process_append_replies(self.res, self.sg, where=DEVICE,
+                                 out=(self.flags if flags is None else flags, self.ferr))
+
+    def check(self, o, G, P, k):
+        """Every buffer of the step against the same step on the oracle."""
+        oargs, ogerr = o.gather_append_args(self.slots, self.peers)
+        assert np.array_equal(from_words(self.args, AE_ARGS), oargs), k
+        assert np.array_equal(self.gerr.cpu().numpy(), ogerr), k
+        orep, oherr = o.handle_append_entries(oargs, None)
+        assert np.array_equal(from_words(self.rep, AE_REPLY), orep), k
+        assert np.array_equal(self.herr.cpu().numpy(), oherr), k
+        # the handler's reply records: the host-assembled records of the items it handled,
+        # slot = peer = -1 for the others (a gather that failed forwards
+        # zeroed args; with no host in between the batch carries them on)
+        # (an item whose gather failed carries zeroed args: the device folds
+        # its record as handled, the host helper below does not build one)
+        gres = from_words(self.res, AE_RESULT)
+        okh = oherr == 0
+        sel = okh & (ogerr == 0)
+        hand = gres[sel][np.argsort(gres["slot"][sel], kind="stable")]
+        want = results_of(self.slots, self.peers, oargs, orep, np.where(ogerr == 0, oherr, 1), G, P)[0]
+        assert np.array_equal(hand, want), k
+        assert (gres["slot"][~okh] == -1).all(), k
+        # the fold over exactly what the device folded
+        of, oferr = o.process_append_replies(gres, self.seg)
+        assert np.array_equal(self.flags.cpu().numpy(), of) and np.array_equal(self.ferr.cpu().numpy(), oferr), k
 
 
 def test_back_to_back_steps_without_host_sync_gpu():
     import torch
     G, P, L, K = 512, 5, 256, 4
     st, lp, _ = synth_tick_state(G, P, L, seed=synth_seed(3) + 9)
-    slots, peers = all_follower_items(lp, G, P)
-    n = len(slots)
-    dev = torch.device("cuda", 0)
-    lib = _abi.lib()
-    z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    args = [z(n, 10) for _ in range(K)]
-    gerr, herr, ferr, flags = ([z(n) for _ in range(K)] for _ in range(4))
-    rep, res = [z(n, 4) for _ in range(K)], [z(n, 8) for _ in range(K)]
-    sl_d, pe_d = torch.from_numpy(slots).to(dev), torch.from_numpy(peers).to(dev)
-    seg = np.concatenate([[0], np.cumsum(np.bincount(slots // P, minlength=G)[lp >= 0])]).astype(np.int64)
-    seg_d = torch.from_numpy(seg).to(dev)
+    steps = [Step(lp, G, P, torch.device("cuda", 0)) for _ in range(K)]
     with Engine(G, P, L) as e:
         e.load_state(st)
-        stream = torch.cuda.ExternalStream(e.stream(), device=dev)
-        e.synchronize()
-        with torch.cuda.stream(stream):
-            torch.cuda._sleep(int(2e8))  # ~0.1 s of device spin ahead of the calls
-        for k in range(K):
-            assert lib.mraft_gather_append_args(e._h, sl_d.data_ptr(), pe_d.data_ptr(), n, args[k].data_ptr(),
-                                                gerr[k].data_ptr(), DEVICE) == 0, _abi.last_error()
-            assert lib.mraft_handle_append_entries_ex(e._h, args[k].data_ptr(), n, None, 0, rep[k].data_ptr(),
-                                                      res[k].data_ptr(), herr[k].data_ptr(), DEVICE) == 0, \
-                _abi.last_error()
-            assert lib.mraft_process_append_replies(e._h, res[k].data_ptr(), n, seg_d.data_ptr(), len(seg) - 1,
-                                                    flags[k].data_ptr(), ferr[k].data_ptr(), DEVICE) == 0, \
-                _abi.last_error()
-        # every call returned with the device still behind the spin: nothing waited on it
-        assert not stream.query(), "a message call waited on the device"
-        e.synchronize()
+        # every call returns with the device still behind the spin: nothing waits on it
+        with behind_spin(e, int(2e8), "a message call"):  # ~0.1 s of device spin ahead of the calls
+            for s in steps:
+                s.enqueue(e)
         got = e.store_state()
     o = Oracle(G, P, L, st)
-    for k in range(K):
-        oargs, ogerr = o.gather_append_args(slots, peers)
-        assert np.array_equal(args[k].cpu().numpy().view(AE_ARGS).reshape(-1), oargs), k
-        assert np.array_equal(gerr[k].cpu().numpy(), ogerr), k
-        orep, oherr = o.handle_append_entries(oargs, None)
-        assert np.array_equal(rep[k].cpu().numpy().view(AE_REPLY).reshape(-1), orep), k
-        assert np.array_equal(herr[k].cpu().numpy(), oherr), k
-        # the handler's reply records: the host-assembled records of the items it handled,
-        # slot = peer = -1 for the others (a gather that failed forwards
-        # zeroed args; with no host in between the batch carries them on)
-        # (an item whose gather failed carries zeroed args: the device folds
-        # its record as handled, the host helper below does not build one)
-        gres = res[k].cpu().numpy().view(AE_RESULT).reshape(-1)
-        okh = oherr == 0
-        sel = okh & (ogerr == 0)
-        hand = gres[sel][np.argsort(gres["slot"][sel], kind="stable")]
-        want = results_of(slots, peers, oargs, orep, np.where(ogerr == 0, oherr, 1), G, P)[0]
-        assert np.array_equal(hand, want), k
-        assert (gres["slot"][~okh] == -1).all(), k
-        # the fold over exactly what the device folded
-        of, oferr = o.process_append_replies(gres, seg)
-        assert np.array_equal(flags[k].cpu().numpy(), of) and np.array_equal(ferr[k].cpu().numpy(), oferr), k
+    for k, s in enumerate(steps):
+        s.check(o, G, P, k)
     assert_states_equal(got, o.state(), G, P, L, f"{K} steps, no host sync")
 
 
@@ -95,59 +100,20 @@ def test_growing_batches_without_host_sync_gpu():
     import torch
     G, P, L, K = 1024, 5, 256, 4
     st, lp, _ = synth_tick_state(G, P, L, seed=synth_seed(3) + 11)
-    dev = torch.device("cuda", 0)
-    lib = _abi.lib()
-    z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    batches = []
-    for k in range(K):
-        gk = G * (k + 1) // K                      # groups [0, gk): a strictly larger batch each step
-        lpk = np.where(np.arange(G) < gk, lp, -1).astype(np.int32)
-        slots, peers = all_follower_items(lpk, G, P)
-        n = len(slots)
-        seg = np.concatenate([[0], np.cumsum(np.bincount(slots // P, minlength=G)[lpk >= 0])]).astype(np.int64)
-        batches.append(dict(slots=slots, peers=peers, n=n, seg=seg,
-                            sl=torch.from_numpy(slots).to(dev), pe=torch.from_numpy(peers).to(dev),
-                            sg=torch.from_numpy(seg).to(dev), args=z(n, 10), gerr=z(n), herr=z(n), ferr=z(n),
-                            flags=z(n), rep=z(n, 4), res=z(n, 8)))
-    assert all(batches[k]["n"] > batches[k - 1]["n"] for k in range(1, K))
+    # groups [0, G * (k + 1) / K): a strictly larger batch each step
+    steps = [Step(np.where(np.arange(G) < G * (k + 1) // K, lp, -1).astype(np.int32), G, P, torch.device("cuda", 0))
+             for k in range(K)]
+    assert all(steps[k].n > steps[k - 1].n for k in range(1, K))
     torch.cuda.synchronize()
     with Engine(G, P, L) as e:
         e.load_state(st)
-        e.synchronize()
-        stream = torch.cuda.ExternalStream(e.stream(), device=dev)
-        with torch.cuda.stream(stream):
-            torch.cuda._sleep(int(2e8))  # ~0.1 s of device spin ahead of the calls
-        for b in batches:
-            n = b["n"]
-            assert lib.mraft_gather_append_args(e._h, b["sl"].data_ptr(), b["pe"].data_ptr(), n, b["args"].data_ptr(),
-                                                b["gerr"].data_ptr(), DEVICE) == 0, _abi.last_error()
-            assert lib.mraft_handle_append_entries_ex(e._h, b["args"].data_ptr(), n, None, 0, b["rep"].data_ptr(),
-                                                      b["res"].data_ptr(), b["herr"].data_ptr(), DEVICE) == 0, \
-                _abi.last_error()
-            assert lib.mraft_process_append_replies(e._h, b["res"].data_ptr(), n, b["sg"].data_ptr(), len(b["seg"]) - 1,
-                                                    b["flags"].data_ptr(), b["ferr"].data_ptr(), DEVICE) == 0, \
-                _abi.last_error()
-        assert not stream.query(), "a growing message call waited on the device"
-        e.synchronize()
+        with behind_spin(e, int(2e8), "a growing message call"):
+            for s in steps:
+                s.enqueue(e)
         got = e.store_state()
     o = Oracle(G, P, L, st)
-    for k, b in enumerate(batches):
-        oargs, ogerr = o.gather_append_args(b["slots"], b["peers"])
-        assert np.array_equal(b["args"].cpu().numpy().view(AE_ARGS).reshape(-1), oargs), k
-        assert np.array_equal(b["gerr"].cpu().numpy(), ogerr), k
-        orep, oherr = o.handle_append_entries(oargs, None)
-        assert np.array_equal(b["rep"].cpu().numpy().view(AE_REPLY).reshape(-1), orep), k
-        assert np.array_equal(b["herr"].cpu().numpy(), oherr), k
-        # (as in test_back_to_back_steps_without_host_sync_gpu: an item whose
-        # gather failed carries zeroed args on to the handler and the fold)
-        gres = b["res"].cpu().numpy().view(AE_RESULT).reshape(-1)
-        okh = oherr == 0
-        sel = okh & (ogerr == 0)
-        want = results_of(b["slots"], b["peers"], oargs, orep, np.where(ogerr == 0, oherr, 1), G, P)[0]
-        assert np.array_equal(gres[sel][np.argsort(gres["slot"][sel], kind="stable")], want), k
-        assert (gres["slot"][~okh] == -1).all(), k
-        of, oferr = o.process_append_replies(gres, b["seg"])
-        assert np.array_equal(b["flags"].cpu().numpy(), of) and np.array_equal(b["ferr"].cpu().numpy(), oferr), k
+    for k, s in enumerate(steps):
+        s.check(o, G, P, k)
     assert_states_equal(got, o.state(), G, P, L, f"{K} growing steps, no host sync")
 
 
@@ -159,38 +125,22 @@ def test_back_to_back_copies_without_host_sync_gpu():
     import torch
     G, P, L, K = 1024, 5, 512, 5
     st, lp, _ = synth_tick_state(G, P, L, seed=synth_seed(3) + 10)
-    slots, peers = all_follower_items(lp, G, P)
-    n = len(slots)
     dev = torch.device("cuda", 0)
-    lib = _abi.lib()
     copies = [{k: torch.from_numpy(v.copy()).to(dev) for k, v in st.items()} for _ in range(K)]
-    z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
-    args, gerr, herr, ferr, flags, rep, res = z(n, 10), z(n), z(n), z(n), z(n), z(n, 4), z(n, 8)
-    fl_all = z(K, n)
-    sl_d, pe_d = torch.from_numpy(slots).to(dev), torch.from_numpy(peers).to(dev)
-    seg = np.concatenate([[0], np.cumsum(np.bincount(slots // P, minlength=G)[lp >= 0])]).astype(np.int64)
-    seg_d = torch.from_numpy(seg).to(dev)
+    s = Step(lp, G, P, dev)
+    fl_all = torch.zeros((K, s.n), dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
     with Engine(G, P, L, alloc=False) as e:
         e.bind(copies[0])
-        stream = torch.cuda.ExternalStream(e.stream(), device=dev)
-        with torch.cuda.stream(stream):
-            torch.cuda._sleep(int(2e8))
-        for k in range(K):
-            e.bind(copies[k])
-            assert lib.mraft_gather_append_args(e._h, sl_d.data_ptr(), pe_d.data_ptr(), n, args.data_ptr(),
-                                                gerr.data_ptr(), DEVICE) == 0
-            assert lib.mraft_handle_append_entries_ex(e._h, args.data_ptr(), n, None, 0, rep.data_ptr(),
-                                                      res.data_ptr(), herr.data_ptr(), DEVICE) == 0
-            assert lib.mraft_process_append_replies(e._h, res.data_ptr(), n, seg_d.data_ptr(), len(seg) - 1,
-                                                    fl_all[k].data_ptr(), ferr.data_ptr(), DEVICE) == 0
-        assert not stream.query(), "a message call waited on the device"
-        e.synchronize()
+        with behind_spin(e, int(2e8), "a message call"):
+            for k in range(K):
+                e.bind(copies[k])
+                s.enqueue(e, flags=fl_all[k])
     o = Oracle(G, P, L, st)
-    oargs, ogerr = o.gather_append_args(slots, peers)
+    oargs, ogerr = o.gather_append_args(s.slots, s.peers)
     assert (ogerr == 0).all()
     orep, oherr = o.handle_append_entries(oargs, None)
-    ores, oseg = results_of(slots, peers, oargs, orep, oherr, G, P)
+    ores, oseg = results_of(s.slots, s.peers, oargs, orep, oherr, G, P)
     of, _ = o.process_append_replies(ores, oseg)
     want = o.state()
     for k in range(K):

@@ -11,19 +11,17 @@ process each on the small-grid library (libmraft_hip_grid1.so: two cycle
 buffers at L = 64, so the deferred launch's other workgroups return before the
 count-out) and on the bounds-checking library (libmraft_hip_dbg.so, its three
 violation counters at 0)."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import handler_cases as hc
+from gpu_support import behind_spin, run_cases_child
 from oracle_lib import Oracle, assert_states_equal
 
-from multiraft_amd import DEVICE, Engine, _abi
-from multiraft_amd._abi import AE_REPLY, AE_RESULT
+from multiraft_amd import DEVICE, Engine
+from multiraft_amd._abi import AE_REPLY, AE_RESULT, from_words, to_words
 
 pytestmark = pytest.mark.gpu
 
@@ -83,44 +81,25 @@ def test_device_buffers_back_to_back_gpu(name):
         rep, err = o.handle_append_entries(a, None)
         want.append((rep, err, hc.ex_records(a, rep, err, P)))
     dev = torch.device("cuda", 0)
-    lib = _abi.lib()
-    bufs = []
-    for a in batches:
-        n = len(a)
-        bufs.append((torch.from_numpy(np.ascontiguousarray(a).view(np.int32).reshape(n, 10).copy()).to(dev),
-                     torch.full((n, 4), -1, dtype=torch.int32, device=dev),
-                     torch.full((n, 8), -1, dtype=torch.int32, device=dev),
-                     torch.full((n,), -1, dtype=torch.int32, device=dev)))
+    fill = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device=dev)  # noqa: E731
+    bufs = [(to_words(a, dev), fill(len(a), 4), fill(len(a), 8), fill(len(a))) for a in batches]
     with Engine(G, P, L) as e:
         e.load_state(fam["st"])
-        stream = torch.cuda.ExternalStream(e.stream(), device=dev)
-        e.synchronize()
-        with torch.cuda.stream(stream):
-            torch.cuda._sleep(int(1e8))  # device spin ahead of the calls
-        for a, (a_d, rep_d, res_d, err_d) in zip(batches, bufs):
-            assert lib.mraft_handle_append_entries_ex(e._h, a_d.data_ptr(), len(a), None, 0, rep_d.data_ptr(),
-                                                      res_d.data_ptr(), err_d.data_ptr(), DEVICE) == 0, _abi.last_error()
-        assert not stream.query(), "a handler call waited on the device"
-        e.synchronize()
+        with behind_spin(e, what="a handler call"):
+            for a_d, rep_d, res_d, err_d in bufs:
+                e.handle_append_entries(a_d, None, results=True, where=DEVICE, out=(rep_d, res_d, err_d))
         got = e.store_state()
     for k, ((rep, err, res), (_, rep_d, res_d, err_d)) in enumerate(zip(want, bufs)):
         assert np.array_equal(err_d.cpu().numpy(), err), (name, k)
-        assert np.array_equal(rep_d.cpu().numpy().view(AE_REPLY).reshape(-1), rep), (name, k)
-        assert np.array_equal(res_d.cpu().numpy().view(AE_RESULT).reshape(-1), res), (name, k)
+        assert np.array_equal(from_words(rep_d, AE_REPLY), rep), (name, k)
+        assert np.array_equal(from_words(res_d, AE_RESULT), res), (name, k)
     assert_states_equal(got, o.state(), G, P, L, f"{name}: two device calls back to back")
 
 
 def _child(libpath):
-    assert os.path.exists(libpath), "build() makes the test libraries"
-    env = dict(os.environ, MRAFT_LIB=libpath)
-    env.pop("MRAFT_DEFER_GRID_MIN", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "handler_cases.py")], env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert r.stdout.strip(), r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_cases_child(os.path.join(ROOT, "tests", "handler_cases.py"), libpath, drop_env=("MRAFT_DEFER_GRID_MIN",))
     assert [tuple(c[:3]) for c in out["cases"]] == RUNS, "the child ran another list"
-    assert all(c[4] is True and c[3] >= 1 for c in out["cases"]), ([c for c in out["cases"] if not c[4]], r.stderr[-3000:])
-    assert r.returncode == 0, r.stderr[-3000:]
+    assert all(c[4] is True and c[3] >= 1 for c in out["cases"]), [c for c in out["cases"] if not c[4]]
     return out
 
 

@@ -24,8 +24,8 @@ import pass_cases as pc
 from message_cases import all_follower_items, external_entries, results_of
 from oracle_lib import Oracle, assert_states_equal
 
-from multiraft_amd import DEVICE, TICK_AUTO, TICK_FULL, TICK_LIGHT, Engine, _abi
-from multiraft_amd._abi import AE_ENTRIES_SORTED, AE_REPLY
+from multiraft_amd import DEVICE, TICK_AUTO, TICK_FULL, TICK_LIGHT, Engine
+from multiraft_amd._abi import AE_ENTRIES_SORTED, AE_REPLY, from_words, to_words
 
 pytestmark = pytest.mark.gpu
 
@@ -239,17 +239,15 @@ def test_value_layouts_device_gpu(layout):
     big[base_off:base_off + len(buf)] = torch.from_numpy(buf).to(dev)
     buf_d = big[base_off:base_off + len(buf)]
     assert buf_d.data_ptr() % 16 == 4 * base_off
-    args_d = torch.from_numpy(batch.view(np.int32).reshape(n, -1).copy()).to(dev)
+    args_d = to_words(batch, dev)
     rep_d = torch.zeros((n, AE_REPLY.itemsize // 4), dtype=torch.int32, device=dev)
     err_d = torch.zeros(n, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()   # the fills and copies ran on torch's stream, the engine has its own
     with Engine(G, P, L) as e:
         e.load_state(c.state)
-        assert _abi.lib().mraft_handle_append_entries_ex(e._h, args_d.data_ptr(), n, buf_d.data_ptr(), len(buf),
-                                                         rep_d.data_ptr(), None, err_d.data_ptr(), DEVICE) == 0, \
-            _abi.last_error()
+        e.handle_append_entries(args_d, buf_d, where=DEVICE, out=(rep_d, None, err_d))
         e.synchronize()
-        rep, herr = rep_d.cpu().numpy().view(AE_REPLY).reshape(-1), err_d.cpu().numpy()
+        rep, herr = from_words(rep_d, AE_REPLY), err_d.cpu().numpy()
         orep, oherr = o.handle_append_entries(batch, buf)
         bad = np.flatnonzero((herr != oherr) | (rep != orep))
         assert len(bad) == 0, f"{c.name} {layout}: replies at {bad[:8]}"

@@ -16,12 +16,13 @@ import ctypes
 import numpy as np
 import pytest
 
+from gpu_support import behind_spin
 from oracle_lib import assert_states_equal
 from timers_cases import CFG, due_timers, leaders_in_place_state
 from timers_model import TimersModel
 
 from multiraft_amd import DEVICE, Engine, _abi
-from multiraft_amd._abi import LEADER, NOTE_RV_FOLDED, NOTE_RV_HANDLED, RV_ARGS, RV_RESULT
+from multiraft_amd._abi import LEADER, NOTE_RV_FOLDED, NOTE_RV_HANDLED, RV_ARGS, RV_RESULT, to_words
 
 pytestmark = pytest.mark.gpu
 
@@ -31,25 +32,15 @@ SPIN = int(2e8)  # ~0.1 s of device spin ahead of the calls
 
 
 def on_device(a):
-    """A device copy of a numpy array (records: their bytes)."""
+    """A device copy of a numpy array (records: their words)."""
     import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.uint8) if a.dtype.fields else a).cuda()
+    return to_words(a, "cuda") if a.dtype.fields else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def same_timers(e, m, ctx):
     for name, a, b in zip(("election_due", "heartbeat_due"), e.timers_store(), (m.ed, m.hd)):
         bad = np.nonzero(a != b)[0][:8]
         assert not len(bad), f"{ctx}: {name} differs at {bad}: {a[bad]} vs {b[bad]}"
-
-
-def spin(e):
-    import torch
-    stream = torch.cuda.ExternalStream(e.stream(), device=torch.device("cuda", 0))
-    e.synchronize()
-    with torch.cuda.stream(stream):
-        torch.cuda._sleep(SPIN)
-    return stream
 
 
 def vote_records(e, o, st, G, P):
@@ -105,23 +96,19 @@ def test_timer_calls_only_enqueue(G, P, L):
         lists = [torch.full((gp,), -7, dtype=torch.int32, device="cuda") for _ in range(4)]
         counts = [torch.full((1,), -7, dtype=torch.int64, device="cuda") for _ in range(4)]
         o_ed, o_hd = (torch.zeros(gp, dtype=torch.int32, device="cuda") for _ in range(2))
-        src = _abi.MraftTimersSoa(d_ed.data_ptr(), d_hd.data_ptr())
         dst = _abi.MraftTimersSoa(o_ed.data_ptr(), o_hd.data_ptr())
         h = e._h
-        stream = spin(e)
-        assert lib.mraft_timers_load(h, ctypes.byref(src), DEVICE) == 0, _abi.last_error()
-        assert lib.mraft_timers_arm(h, d_arm.data_ptr(), len(arm), T - 10, DEVICE) == 0, _abi.last_error()
-        for k, c in enumerate((cap, gp)):
-            assert lib.mraft_ticker(h, T, lists[2 * k].data_ptr(), c, counts[2 * k].data_ptr(),
-                                    lists[2 * k + 1].data_ptr(), c, counts[2 * k + 1].data_ptr(), DEVICE) == 0, \
-                _abi.last_error()
-        for kind, (r, oc, ie) in ((NOTE_RV_HANDLED, d_handled), (NOTE_RV_FOLDED, d_tallied)):
-            assert lib.mraft_timers_note(h, kind, r.data_ptr(), oc.data_ptr(), ie.data_ptr(), len(ie), T + 1,
-                                         DEVICE) == 0, _abi.last_error()
-        assert lib.mraft_timers_store(h, ctypes.byref(dst), DEVICE) == 0, _abi.last_error()
-        # every call returned with the device still behind the spin: nothing waited on it
-        assert not stream.query(), "a timer call waited on the device"
-        e.synchronize()
+        # every call returns with the device still behind the spin: nothing waits on it
+        with behind_spin(e, SPIN, "a timer call"):
+            e.timers_load(d_ed, d_hd, where=DEVICE)
+            e.timers_arm(d_arm, T - 10, where=DEVICE)
+            for k, c in enumerate((cap, gp)):   # the ticker and the store: host wrappers only, so raw
+                assert lib.mraft_ticker(h, T, lists[2 * k].data_ptr(), c, counts[2 * k].data_ptr(),
+                                        lists[2 * k + 1].data_ptr(), c, counts[2 * k + 1].data_ptr(), DEVICE) == 0, \
+                    _abi.last_error()
+            for kind, (r, oc, ie) in ((NOTE_RV_HANDLED, d_handled), (NOTE_RV_FOLDED, d_tallied)):
+                e.timers_note(kind, r, oc, ie, T + 1, where=DEVICE)
+            assert lib.mraft_timers_store(h, ctypes.byref(dst), DEVICE) == 0, _abi.last_error()
         # the model, with the same calls
         m.load(ed, hd)
         m.arm(arm, T - 10)
@@ -163,11 +150,9 @@ def test_clock_steps_only_enqueue(G, P, L, mode):
         m.load(ed, hd)
         outs = [{n: torch.full((G,), 77, dtype=torch.uint8 if n == "cand_mask" else torch.int32, device="cuda")
                  for n in OUTS} for _ in range(K)]
-        stream = spin(e)
-        for k in range(K):
-            e.clock_step(T + k, bool(k % 2), where=DEVICE, out=outs[k])
-        assert not stream.query(), "a clock step waited on the device"
-        e.synchronize()
+        with behind_spin(e, SPIN, "a clock step"):
+            for k in range(K):
+                e.clock_step(T + k, bool(k % 2), where=DEVICE, out=outs[k])
         for k in range(K):
             want = m.clock_step(T + k, bool(k % 2))
             for n in OUTS:

@@ -23,15 +23,14 @@ sys.path.insert(0, ROOT)
 def main():
     import torch
 
-    from multiraft_amd import DEVICE, Engine, _abi, synth_seed, synth_tick_state
+    from multiraft_amd import DEVICE, Engine, synth_seed, synth_tick_state
     G, P, L = 65536, 5, 4096
     reps = int(os.environ.get("REPS", 4))
     st, lp, _ = synth_tick_state(G, P, L, seed=synth_seed(3))
     dev = torch.device("cuda", 0)
     master = {k: torch.from_numpy(v).to(dev) for k, v in st.items()}
     copy = {k: v.clone() for k, v in master.items()}
-    lib = _abi.lib()
-    ldr = (np.arange(G) * P + lp).repeat(P - 1)
+    ldr =(np.arange(G) * P + lp).repeat(P - 1)
     q = np.tile(np.arange(P - 1), G)
     peers = np.where(q < np.repeat(lp, P - 1), q, q + 1)
     keep = np.repeat(lp >= 0, P - 1)
@@ -65,11 +64,9 @@ def main():
         e.bind(copy)
         c, d, f = ev(), ev(), ev()
         c.record(st_)
-        assert lib.mraft_gather_append_args(e._h, slots_d.data_ptr(), peers_d.data_ptr(), n, args.data_ptr(),
-                                            gerr.data_ptr(), DEVICE) == 0, _abi.last_error()
+        e.gather_append_args(slots_d, peers_d, where=DEVICE, out=(args, gerr))
         d.record(st_)
-        assert lib.mraft_handle_append_entries_ex(e._h, args.data_ptr(), n, None, 0, rep.data_ptr(), res.data_ptr(),
-                                                  herr.data_ptr(), DEVICE) == 0, _abi.last_error()
+        e.handle_append_entries(args, None, results=True, where=DEVICE, out=(rep, res, herr))
         f.record(st_)
         e.synchronize()
         if r:  # rep 0 warms up
