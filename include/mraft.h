@@ -171,6 +171,7 @@ typedef struct {
  * per replica:
  *   Make (mraft_create), InstallSnapshot installing a new log: 1;
  *   mraft_load_state, mraft_restore: computed from the terms;
+ *   mraft_crash: kept when 1, computed from the terms when 0;
  *   Start (raft.go:96-100): cleared when term(last) > currentTerm;
  *   HandleAppendEntries appending from Index k (truncate + append,
  *   raft_append_entry.go:149-155): set to the args' MRAFT_AE_ENTRIES_SORTED
@@ -673,7 +674,7 @@ int mraft_election_rounds(mraft_engine *h, const uint8_t *cand_mask,
 /* Optional capabilities of this build, a bitmask (the ABI version says which
  * structs and entry points exist; a feature bit says a later addition that
  * changed none of them is present). */
-enum { MRAFT_FEATURE_TIMERS = 1, MRAFT_FEATURE_REACH = 2 };
+enum { MRAFT_FEATURE_TIMERS = 1, MRAFT_FEATURE_REACH = 2, MRAFT_FEATURE_CRASH = 4 };
 int32_t mraft_features(void);
 
 /* Timer state: per replica slot the absolute time, in caller-defined clock
@@ -721,7 +722,8 @@ int mraft_timers_disable(mraft_engine *h);
 int mraft_timers_load(mraft_engine *h, const mraft_timers_soa *src, int32_t where);
 int mraft_timers_store(mraft_engine *h, const mraft_timers_soa *dst, int32_t where);
 /* Arms both timers of n slots at `now`, as Make does for a restarted replica
- * (call it after mraft_restore). Slots outside [0, G*P) are skipped. */
+ * (call it after mraft_restore or mraft_crash). Slots outside [0, G*P) are
+ * skipped. */
 int mraft_timers_arm(mraft_engine *h, const int32_t *slots, int64_t n, int32_t now,
                      int32_t where);
 
@@ -874,6 +876,51 @@ int mraft_read_persistent(mraft_engine *h, const int32_t *slots, int64_t n,
  * MRAFT_ITEM_LOG_FULL (more than L entries), MRAFT_ITEM_DUP_SLOT. */
 int mraft_restore(mraft_engine *h, const mraft_persistent *in, int64_t n,
                   const int32_t *terms, int64_t n_terms, int32_t *item_err);
+
+/* A deadline no `now` (<= 2^30) reaches: the timers of a replica that is down. */
+#define MRAFT_TIMER_NEVER INT32_MAX
+
+/* Crash of n co-resident replicas in place (MRAFT_FEATURE_CRASH; config.go
+ * crash1, and the Make + readPersist half of start1). The reference persists
+ * after every assignment to currentTerm, votedFor or the log before the
+ * handler returns (raft.go:101, raft_append_entry.go:72,111,
+ * raft_election.go:15,45,57, raft_snapshot.go:12,26,47,64), so between two
+ * calls a replica's Persister holds exactly its live persistent fields, and
+ * crash + Make + readPersist moves no log word: it resets the volatile
+ * fields. For every item whose slot is in [0, G*P) and whose replica has
+ * 0 <= lastIndex - dummyIndex < L:
+ *  - state Follower; commitIndex = lastApplied = dummyIndex (raft.go:79-80);
+ *    matchIndex[*] = nextIndex[*] = 0; grantedVotes 0; has_snapshot 0;
+ *    persist_dirty 0;
+ *  - terms_sorted stays 1 when it is 1 (the proof is taken as it stands);
+ *    when it is 0 it is recomputed from the ring over Index dummy+1 .. last;
+ *  - currentTerm, votedFor, dummyIndex, lastIndex, log_head and every word
+ *    of log_term are not written;
+ *  - with timers enabled, election_due = heartbeat_due = MRAFT_TIMER_NEVER:
+ *    the replica is down until mraft_timers_arm (Make's two NewTimer calls)
+ *    restarts it. Without timers the call does the state part only.
+ * item_err (optional): MRAFT_ITEM_BAD_SLOT (slot out of range),
+ * MRAFT_ITEM_BAD_STATE (the log bounds are broken); nothing is written for
+ * such an item. A slot may repeat: the result is the same, there is no
+ * MRAFT_ITEM_DUP_SLOT. n == 0 with NULL pointers is MRAFT_OK; MRAFT_E_NOSTATE
+ * without bound state. Host or device buffers; with MRAFT_DEVICE the call only
+ * enqueues on the engine stream (one launch, timers or not).
+ *
+ * Downtime: while a replica is down the host clears its reachability bit
+ * (mraft_set_reachable), as crash1 itself calls disconnect(). With the bit
+ * clear nothing reaches the replica and rule E of mraft_clock_step does not
+ * re-arm it; its deadlines are never due, so it neither times out nor raises
+ * its term. mraft_crash followed at once by mraft_timers_arm is a crash and
+ * restart within one tick.
+ *
+ * Relation to the round trip: the result equals mraft_read_persistent ->
+ * mraft_restore on the same slots in every array except log_head and the
+ * physical placement of the log words (restore starts a new ring at 0, this
+ * call keeps the head), with the same logical log. persist_dirty is cleared,
+ * not reported: a host that mirrors a Persister of its own calls
+ * mraft_collect_persist first. */
+int mraft_crash(mraft_engine *h, const int32_t *slots, int64_t n, int32_t *item_err,
+                int32_t where);
 
 /* Host-only codec of one replica's persistent state (the bytes a Persister
  * holds, persister.go:39-64). Not gob (labgob.go): little-endian

@@ -39,6 +39,8 @@ FANIN_ORDERED = 2
 COMM_ID_BYTES = 128
 FEATURE_TIMERS = 1  # mraft_features
 FEATURE_REACH = 2   # mraft_set_reachable / mraft_get_reachable
+FEATURE_CRASH = 4   # mraft_crash
+TIMER_NEVER = 2**31 - 1  # MRAFT_TIMER_NEVER: the deadlines of a replica that is down
 (NOTE_AE_HANDLED, NOTE_IS_HANDLED, NOTE_RV_HANDLED, NOTE_AE_FOLDED, NOTE_IS_FOLDED,
  NOTE_RV_FOLDED) = range(6)  # mraft_timers_note kinds
 CLOCK_SEND_ALL = 1
@@ -119,6 +121,7 @@ ABI_SYMBOLS = (
     "mraft_features", "mraft_timer_draw", "mraft_timers_enable", "mraft_timers_disable",
     "mraft_timers_load", "mraft_timers_store", "mraft_timers_arm", "mraft_ticker",
     "mraft_timers_note", "mraft_clock_step", "mraft_set_reachable", "mraft_get_reachable",
+    "mraft_crash",
 )
 SYNTH_SYMBOLS = ("mraft_synth_tick_state", "mraft_synth_fold_batch", "mraft_synth_election_state")
 
@@ -190,6 +193,7 @@ _SIGS = {
     "mraft_clock_step": (ctypes.c_int, [_vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "mraft_set_reachable": (ctypes.c_int, [_vp, _vp, _i32]),
     "mraft_get_reachable": (ctypes.c_int, [_vp, _vp, _i32]),
+    "mraft_crash": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i32]),
 }
 _SYNTH_SIGS = {
     "mraft_synth_tick_state": (ctypes.c_int, [ctypes.c_uint64, _i32, _i32, _i32, _i32, _i32,

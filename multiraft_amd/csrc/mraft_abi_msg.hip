@@ -382,4 +382,18 @@ int mraft_restore(mraft_engine *h, const mraft_persistent *in, int64_t n, const 
   return MRAFT_OK;
 }
 
+int mraft_crash(mraft_engine *h, const int32_t *slots, int64_t n, int32_t *item_err, int32_t where) {
+  TRY(enter(h));
+  if (n < 0 || (n > 0 && !slots)) return fail(MRAFT_E_INVAL, "null argument");
+  if (n > INT32_MAX) return fail(MRAFT_E_INVAL, "n = %lld items exceeds 2^31 - 1", (long long)n);
+  if (n == 0) return MRAFT_OK;
+  Stage sg(h, where);
+  const int32_t *s = sg.in(slots, n);
+  int32_t *e = sg.out(item_err, n);
+  TRY(sg.status());
+  // one launch, timers or not: the deadline arrays are null without them
+  mraft::launch_crash(dev_of(h), s, n, e, h->tm_ed, h->tm_hd, h->stream);
+  return sg.finish();
+}
+
 }  // extern "C"

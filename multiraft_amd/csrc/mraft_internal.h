@@ -98,6 +98,9 @@ void launch_read_persistent_terms(const Dev &s, const mraft_persistent *hdr, int
                                   int32_t *out, hipStream_t st);
 void launch_restore(const Dev &s, const mraft_persistent *in, int64_t n, const int32_t *terms,
                     const int32_t *err, hipStream_t st);
+// mraft_crash: ed / hd are the timer arrays, both or neither (null: no timers).
+void launch_crash(const Dev &s, const int32_t *slots, int64_t n, int32_t *err, int32_t *ed, int32_t *hd,
+                  hipStream_t st);
 void launch_export(const Dev &s, const int32_t *lpeer, int32_t *commit, int32_t *term_leader,
                    hipStream_t st);
 

@@ -506,6 +506,46 @@ __global__ __launch_bounds__(256) void k_restore(Dev s, const mraft_persistent *
   }
 }
 
+// crash1 (config.go:113) + Make + readPersist in place (mraft_crash): wave per
+// item. The persistent fields are live in HBM already (the reference persists
+// before every handler returns), so the Make half of k_restore is all there is:
+// no log word moves, the ring keeps its head. ed / hd: the timer arrays, or
+// null without timers (a down replica's deadlines are never due).
+__global__ __launch_bounds__(256) void k_crash(Dev s, const int32_t *__restrict__ slots, int64_t n,
+                                               int32_t *__restrict__ err, int32_t *__restrict__ ed,
+                                               int32_t *__restrict__ hd) {
+  const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  if (i >= n) return;
+  const int64_t sl = slots[i];
+  int e = MRAFT_ITEM_OK, d = 0, last = 0;
+  if (sl < 0 || sl >= (int64_t)s.G * s.P) {
+    e = MRAFT_ITEM_BAD_SLOT;
+  } else {
+    d = s.dummy[sl]; last = s.last[sl];
+    if ((int64_t)last - d < 0 || (int64_t)last - d >= s.L) e = MRAFT_ITEM_BAD_STATE;
+  }
+  if (err && lane_id() == 0) err[i] = e;
+  if (e) return;
+  // the proof is taken as it stands; without one, from the ring (a head outside
+  // the ring proves nothing). Repeated slots write the same words.
+  if (!s.srt[sl]) {
+    const int h = s.head[sl];
+    if (h >= 0 && h < s.L && wave_terms_sorted(s.log + sl * s.L, d, h, s.L, d + 1, last) && lane_id() == 0)
+      s.srt[sl] = 1;
+  }
+  if (lane_id() == 0) {
+    s.role[sl] = kFollower;                                            // raft.go:58
+    s.commit[sl] = d;                                                  // :79
+    s.applied[sl] = d;                                                 // :80
+    s.votes[sl] = 0;
+    s.hsnap[sl] = 0;                                                   // Make: no snapshot pending
+    if (s.pdirty) s.pdirty[sl] = 0;
+    if (ed) { ed[sl] = MRAFT_TIMER_NEVER; hd[sl] = MRAFT_TIMER_NEVER; }
+  }
+  for (int j = lane_id(); j < 2 * s.P; j += 64)                        // :64-65 make([]int, P)
+    (j < s.P ? s.match[sl * s.P + j] : s.next[sl * s.P + j - s.P]) = 0;
+}
+
 // terms_sorted of every replica from its log (mraft_load_state): wave per slot.
 __global__ __launch_bounds__(256) void k_terms_sorted(Dev s) {
   const int64_t gp = (int64_t)s.G * s.P;
@@ -641,6 +681,11 @@ void launch_read_persistent_terms(const Dev &s, const mraft_persistent *hdr, int
 void launch_restore(const Dev &s, const mraft_persistent *in, int64_t n, const int32_t *terms, const int32_t *err,
                     hipStream_t st) {
   launch_items(k_restore, n * 64, st, s, in, n, terms, err);
+}
+
+void launch_crash(const Dev &s, const int32_t *slots, int64_t n, int32_t *err, int32_t *ed, int32_t *hd,
+                  hipStream_t st) {
+  launch_items(k_crash, n * 64, st, s, slots, n, err, ed, hd);
 }
 
 void launch_export(const Dev &s, const int32_t *lpeer, int32_t *commit, int32_t *term_leader, hipStream_t st) {

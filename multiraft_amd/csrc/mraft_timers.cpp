@@ -6,7 +6,7 @@
 
 extern "C" {
 
-int32_t mraft_features(void) { return MRAFT_FEATURE_TIMERS | MRAFT_FEATURE_REACH; }
+int32_t mraft_features(void) { return MRAFT_FEATURE_TIMERS | MRAFT_FEATURE_REACH | MRAFT_FEATURE_CRASH; }
 
 int32_t mraft_timer_draw(const mraft_timer_config *cfg, int64_t slot, int32_t now) {
   if (!cfg || !mraft::timer_config_ok(*cfg)) return -1;

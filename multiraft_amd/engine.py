@@ -415,6 +415,21 @@ class Engine(BatchCalls):
             _ck(rc, "mraft_get_reachable")
         return out if rc == 1 else None
 
+    # ---- crash in place (config.go crash1 / start1) ------------------------
+    def crash(self, slots, where: int = HOST, out=None):
+        """config.go's crash1 for co-resident replicas (mraft_crash): the
+        volatile fields of `slots` reset as Make + readPersist leave them,
+        the persistent ones and the log untouched, and with timers enabled
+        both deadlines _abi.TIMER_NEVER, so the replica is down until
+        `timers_arm` restarts it (clear its reachability bit meanwhile).
+        Returns item_err. where / out as in _calls: host arrays are
+        synchronous; with DEVICE the call only enqueues, and out=(None,)
+        passes NULL for item_err."""
+        slots = _in(slots, np.int32, where)
+        (err,) = _outs(out, (np.int32,), len(slots), where, slots)
+        self._invoke("crash", ptr(slots), len(slots), ptr(err), where=where)
+        return err
+
     # ---- multi-GPU fan-in (SURVEY.md §8e; include/mraft.h) -----------------
     def comm_init(self, nranks: int, rank: int, uid: bytes) -> int:
         """ncclCommInitRank on this engine's device (collective over the ranks):
